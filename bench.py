@@ -5,8 +5,13 @@ One "step" = restore one batch per GPU: DaCLIP encode_image(control=True) -> noi
 Inputs are synthetic (random-init weights of the real architectures, synthetic LQ images)
 and resident in HBM before the timed region. Weights are created on rank 0 and broadcast
 over RCCL. Usage (driver contract):
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+A plain run does only what the headline figure needs: set up, W warmup steps, K timed steps,
+the optional output dump, the JSON result line. Everything else the benchmark measures (the
+roofline replays, PSNR against the reference fixture, the extra dtypes under `modes`, the extra
+configurations under `lines`, the CPU baseline) runs only with --full, where --no-roofline,
+--no-psnr, --modes, --lines and --no-cpu-baseline select among them as before.
 Run the first way with N > 1 (no WORLD_SIZE in the environment), bench.py starts the N ranks
 itself: one `torch.distributed.run` child on 127.0.0.1, launched before any GPU call, whose
 exit code it returns. Under a launcher, WORLD_SIZE must equal --gpus.
@@ -44,6 +49,15 @@ def parse():
     p.add_argument("--batch", type=int, default=None, help="images per GPU (8; wild-ir 2)")
     p.add_argument("--res", type=int, default=None, help="resolution (256; wild-ir 512)")
     p.add_argument("--T", type=int, default=100)
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run every secondary measurement: roofline replays, PSNR "
+                        "vs the reference fixture, --modes, --lines and the CPU baseline (each still has its "
+                        "own switch below); without --full none of them runs and those switches are inert")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step returned (the restored images "
+                        "[global batch, 3, R, R]) to DIR/restored.npy as float32; above 64 MB a fixed seeded "
+                        "sample of its elements. Inputs and noise are seeded, so equal arguments give equal "
+                        "inputs from run to run")
     p.add_argument("--dtype", default="fp16", choices=["bf16", "fp16", "fp32", "fp8"],
                    help="fp16 (default) = IEEE half storage on the f16 MFMA, fp32 accumulation: the "
                         "16-bit mode that holds the north-star 1e-3 dB PSNR bar; bf16 = the same kernels "
@@ -81,6 +95,11 @@ def parse():
     a = p.parse_args()
     if a.gpus < 1:
         p.error("--gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    if not a.full:
+        a.no_roofline = a.no_psnr = a.no_cpu_baseline = True
+        a.modes = a.lines = "none"
     wild = a.model == "wild-ir"
     a.batch = a.batch or (2 if wild else 8)
     a.res = a.res or (512 if wild else 256)
@@ -374,6 +393,22 @@ def timed_steps(step, warmup, steps, ws, dev):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
     return out, el
+
+
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(out, path):
+    """--dump-outputs: the last timed step's return value (what a caller of the timed path
+    receives) as `path`/restored.npy, float32. An output above 64 MB is written as a fixed
+    sample of half that many bytes: its elements at the sorted indices drawn by
+    numpy.random.default_rng(0).integers(0, numel, n), the same for every run of one shape."""
+    os.makedirs(path, exist_ok=True)
+    a = out.detach().to("cpu", torch.float32).contiguous().numpy()
+    if a.nbytes > DUMP_CAP_BYTES:
+        n = DUMP_CAP_BYTES // 2 // a.itemsize
+        a = a.reshape(-1)[np.sort(np.random.default_rng(0).integers(0, a.size, n))]
+    np.save(os.path.join(path, "restored.npy"), a)
 
 
 def profile_class(h, step, kernel_id):
@@ -732,12 +767,17 @@ def main():
     B = lq.shape[0]
     step = make_step(clip, sde, lq, img4clip, lo, n_glob, ws)
     h = unet._h
+    # noise_state draws from torch's generator; the loop's device noise is keyed by the step
+    # count and the global image index. Seeded, equal arguments give equal inputs every run.
+    torch.manual_seed(1000 + lo)
     out, el = timed_steps(step, args.warmup, args.steps, ws, dev)
 
     finite = bool(torch.isfinite(out).all().item())
     if not finite:
         # fp16 storage saturates at 65504: a non-finite restore is an error, never a number.
         raise SystemExit(f"bench: non-finite restored outputs in {args.dtype} mode")
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(out, args.dump_outputs)
     n_launch, mean_ms, fl, by, eager_ms = 0, 0.0, 0.0, 0.0, 0.0
     roof = None
     # The committed PMC passes were collected on the default workload only.

@@ -15,6 +15,6 @@ done
 bash tools/gpu_rfcmp.sh c7ct libab/base.so 3 conv7 || exit 1
 for arm in A B; do
   E=""; [ $arm = A ] && E="DAC_LIB_PATH=libab/base.so"
-  env $E timeout -k 10 300 python -u bench.py --steps 2 --warmup 1 --modes none --lines mixed8 --no-cpu-baseline --no-roofline > $O/p$arm.log 2>&1 || { echo P FAILED; tail -5 $O/p$arm.log; exit 1; }
+  env $E timeout -k 10 300 python -u bench.py --full --steps 2 --warmup 1 --modes none --lines mixed8 --no-cpu-baseline --no-roofline > $O/p$arm.log 2>&1 || { echo P FAILED; tail -5 $O/p$arm.log; exit 1; }
   grep '^{' $O/p$arm.log | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); print("'$arm'", d["value"], d["psnr"]["delta_db"], d["psnr"]["u8_mismatch"], d["lines"][0]["psnr"]["delta_db"])'
 done

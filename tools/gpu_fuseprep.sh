@@ -8,7 +8,7 @@ timeout -k 10 600 python -u -m pytest -x -q --timeout 300 --timeout-method threa
 tail -2 $O/tests.log
 for r in 1 2 3; do
   for f in 0 1; do
-    DAC_FUSE_PREP=$f timeout -k 10 300 python -u bench.py --steps 4 --warmup 1 --modes none --lines none --no-cpu-baseline --no-roofline $([ $r = 1 ] || echo --no-psnr) > $O/b${f}_$r.log 2>&1 || { echo "B$f FAILED"; tail -5 $O/b${f}_$r.log; exit 1; }
+    DAC_FUSE_PREP=$f timeout -k 10 300 python -u bench.py --full --steps 4 --warmup 1 --modes none --lines none --no-cpu-baseline --no-roofline $([ $r = 1 ] || echo --no-psnr) > $O/b${f}_$r.log 2>&1 || { echo "B$f FAILED"; tail -5 $O/b${f}_$r.log; exit 1; }
     grep '^{' $O/b${f}_$r.log | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); p=d.get("psnr") or {}; print("fuse='$f'", d["value"], d["ms_per_step"], p.get("delta_db"), p.get("u8_mismatch"))'
   done
 done

@@ -12,6 +12,6 @@ cp profiles/pmc_traffic.json $O/pmc_traffic.json
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 -u bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-psnr --no-roofline --modes none --lines none > $O/profrun.log 2>&1 || { echo PROF FAILED; tail -20 $O/profrun.log; exit 1; }
 python3 tools/kstats.py $(find $O/prof -name "*kernel_stats.csv" | head -1) > $O/kernel_stats_summary.txt
 head -40 $O/kernel_stats_summary.txt
-timeout -k 10 900 python -u bench.py > $O/bench.log 2>&1 || { echo BENCH FAILED; tail -20 $O/bench.log; exit 1; }
+timeout -k 10 900 python -u bench.py --full > $O/bench.log 2>&1 || { echo BENCH FAILED; tail -20 $O/bench.log; exit 1; }
 grep '^{' $O/bench.log > $O/bench.json
 cut -c1-1500 $O/bench.json

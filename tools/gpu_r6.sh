@@ -15,7 +15,7 @@ if [ "${2:-tests}" = tests ]; then
   timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { echo SMOKE FAILED; tail -20 $O/smoke.log; exit 1; }
   tail -2 $O/smoke.log
 fi
-CMD="bench.py --steps 3 --warmup 1 --modes none --lines none --no-cpu-baseline --no-psnr"
+CMD="bench.py --full --steps 3 --warmup 1 --modes none --lines none --no-cpu-baseline --no-psnr"
 timeout -k 10 300 python -u $CMD > $O/bench_short.log 2>&1 || { echo BENCH FAILED; tail -20 $O/bench_short.log; exit 1; }
 grep '^{' $O/bench_short.log > $O/bench_short.json
 cut -c1-600 $O/bench_short.json
@@ -24,7 +24,7 @@ grep '^{' $O/profrun.log > $O/bench_under_prof.json
 python3 tools/kstats.py $(find $O/prof -name "*kernel_stats.csv" | head -1) > $O/kernel_stats_summary.txt
 head -25 $O/kernel_stats_summary.txt | cut -c1-160
 if [ "${3:-}" = full ]; then
-  timeout -k 10 900 python -u bench.py > $O/bench.log 2>&1 || { echo FULL BENCH FAILED; tail -20 $O/bench.log; exit 1; }
+  timeout -k 10 900 python -u bench.py --full > $O/bench.log 2>&1 || { echo FULL BENCH FAILED; tail -20 $O/bench.log; exit 1; }
   grep '^{' $O/bench.log > $O/bench.json
   cut -c1-800 $O/bench.json
 fi

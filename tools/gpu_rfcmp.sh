@@ -8,7 +8,7 @@ F=${4:-conv3_kernel,rbfuse,conv3i}
 for r in $(seq 1 ${3:-2}); do
   for arm in A B; do
     E=""; [ $arm = A ] && E="DAC_LIB_PATH=$2"
-    env $E timeout -k 10 300 python -u bench.py --steps 3 --warmup 1 --modes none --lines none --no-cpu-baseline --no-psnr > $O/$arm$r.log 2>&1 || { echo "$arm$r FAILED"; tail -5 $O/$arm$r.log; exit 1; }
+    env $E timeout -k 10 300 python -u bench.py --full --steps 3 --warmup 1 --modes none --lines none --no-cpu-baseline --no-psnr > $O/$arm$r.log 2>&1 || { echo "$arm$r FAILED"; tail -5 $O/$arm$r.log; exit 1; }
     grep '^{' $O/$arm$r.log | python3 -c '
 import json,sys
 d=json.loads(sys.stdin.read()); r=d["roofline"]; keys=sys.argv[1].split(",")

@@ -12,6 +12,6 @@ done
 bash tools/gpu_rfcmp.sh v3defer libab/base.so 3 conv3_kernel || exit 1
 for arm in A B; do
   E=""; [ $arm = A ] && E="DAC_LIB_PATH=libab/base.so"
-  env $E timeout -k 10 300 python -u bench.py --steps 2 --warmup 1 --modes none --lines mixed8 --no-cpu-baseline --no-roofline > $O/p$arm.log 2>&1 || { echo P FAILED; tail -5 $O/p$arm.log; exit 1; }
+  env $E timeout -k 10 300 python -u bench.py --full --steps 2 --warmup 1 --modes none --lines mixed8 --no-cpu-baseline --no-roofline > $O/p$arm.log 2>&1 || { echo P FAILED; tail -5 $O/p$arm.log; exit 1; }
   grep '^{' $O/p$arm.log | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); print("'$arm'", d["value"], json.dumps(d.get("psnr")), json.dumps([l.get("psnr") for l in d.get("lines", [])])[:600])'
 done
