@@ -295,6 +295,21 @@ int dac_op_attention(const void* qkv, void* out, int B, int L, int H, int dtype,
   return hipGetLastError() == hipSuccess ? DAC_OK : DAC_E_HIP;
 }
 
+size_t dac_image_metrics_workspace(int B, int C, int H, int W, int crop_border) {
+  return dac::image_metrics_ws_bytes(B, C, H, W, crop_border);
+}
+
+int dac_image_metrics(const float* out, const float* gt, int B, int C, int H, int W, int crop_border,
+                      unsigned char* out_bytes, unsigned char* gt_bytes, double* results,
+                      void* workspace, void* stream) {
+  if (!out || !gt || !out_bytes || !gt_bytes || !results || !workspace ||
+      !dac::image_metrics_ok(B, C, H, W, crop_border))
+    return DAC_E_ARG;
+  dac::image_metrics(out, gt, B, C, H, W, crop_border, out_bytes, gt_bytes, results, workspace,
+                     (hipStream_t)stream);
+  return hipGetLastError() == hipSuccess ? DAC_OK : DAC_E_HIP;
+}
+
 int dac_profile_enable(dac_handle* h, int kernel_id) {
   return guard(h, [&]() -> int {
     h->eng->prof.kernel_id = kernel_id;

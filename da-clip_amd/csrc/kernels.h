@@ -332,4 +332,15 @@ void vit_embed(const void* patch, const float* cls, const float* pos, void* tok,
 template <typename T>
 void rows_to_f32(const void* x, int ld, float* y, int R, int D, hipStream_t st);
 
+// Evaluation metrics on the device (metrics.hip; test.py:131-196): out / gt fp32 [B,C,H,W] RGB ->
+// uint8 [B,H,W,C] BGR (util.tensor2img), then per image, over the window cropped by cb, the
+// 8-double record {sse, n, ssim, sse_y, n_y, ssim_y, nonfinite, 0} in fp64 (SSIM: 11x11 Gaussian
+// window, 'valid' region; Y from the BGR bytes, unrounded). image_metrics_ok: the shapes served
+// (C in {1, 3}, cropped window >= 11 x 11); ws: image_metrics_ws_bytes() bytes (0 for a bad shape).
+bool image_metrics_ok(int B, int C, int H, int W, int cb);
+size_t image_metrics_ws_bytes(int B, int C, int H, int W, int cb);
+void image_metrics(const float* out, const float* gt, int B, int C, int H, int W, int cb,
+                   unsigned char* out_u8, unsigned char* gt_u8, double* results, void* ws,
+                   hipStream_t st);
+
 }  // namespace dac

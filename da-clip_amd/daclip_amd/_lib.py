@@ -29,7 +29,7 @@ DAC_F32, DAC_BF16, DAC_FP8, DAC_F16 = 0, 1, 2, 3
 DAC_SRC_F32, DAC_SRC_F16, DAC_SRC_BF16 = 0, 1, 2
 DAC_POSTERIOR, DAC_SDE = 0, 1
 DAC_COSINE, DAC_LINEAR, DAC_CONSTANT = 0, 1, 2
-DAC_E_MISSING, DAC_E_KEY = -3, -2
+DAC_E_MISSING, DAC_E_KEY, DAC_E_ARG = -3, -2, -1
 DAC_ATTN_Q_PRESCALED = 8
 
 EXPORTS = ["dac_create", "dac_destroy", "dac_set_weight", "dac_finalize_weights",
@@ -37,7 +37,7 @@ EXPORTS = ["dac_create", "dac_destroy", "dac_set_weight", "dac_finalize_weights"
            "dac_sde_schedule", "dac_sde_set_time_scale", "dac_sde_reverse", "dac_build_id",
            "dac_set_noise_offset", "dac_posterior_step", "dac_unet_flops", "dac_encode_flops", "dac_profile_enable",
            "dac_profile_read", "dac_profile_mode", "dac_profile_launch", "dac_profile_graph_ms",
-           "dac_op_attention", "dac_last_error"]
+           "dac_op_attention", "dac_image_metrics_workspace", "dac_image_metrics", "dac_last_error"]
 
 
 class DacConfig(ctypes.Structure):
@@ -90,6 +90,8 @@ def lib() -> ctypes.CDLL:
                                    ctypes.c_char_p, I, ctypes.c_char_p, I]),
         "dac_profile_graph_ms": (I, [P, ctypes.POINTER(D)]),
         "dac_op_attention": (I, [P, P, I, I, I, I, I, P]),
+        "dac_image_metrics_workspace": (ctypes.c_size_t, [I, I, I, I, I]),
+        "dac_image_metrics": (I, [P, P, I, I, I, I, I, P, P, P, P, P]),
         "dac_last_error": (ctypes.c_char_p, [P]),
     }
     for name, (res, args) in sig.items():

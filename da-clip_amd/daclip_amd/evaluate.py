@@ -3,11 +3,14 @@ native path. Same-size images are restored together (one encode + one captured T
 per batch; images are independent, so per-image results do not depend on the grouping).
 
     python -m daclip_amd.evaluate --opt test.yml --lq LQ_DIR [--gt GT_DIR] --out OUT_DIR
-                                  [--synthetic] [--batch 8] [--dtype bf16]
+                                  [--synthetic] [--batch 8] [--dtype bf16] [--metrics device]
 
 Per image: restored PNG (test.py:131-138) and, with GT, PSNR / SSIM / PSNR_Y / SSIM_Y
 (test.py:146-196). LPIPS needs its pretrained network, which is unavailable offline: not
-computed (reported as None).
+computed (reported as None). --metrics host (default) quantises and scores on the host
+(tensor2img + metrics.image_metrics); --metrics device does both in one fp64 HIP call per
+batch (metrics.image_metrics_device) and copies back only the uint8 images and the records;
+it refuses images whose cropped window is under 11x11 (the host path reports NaN there).
 """
 from __future__ import annotations
 
@@ -24,7 +27,7 @@ from PIL import Image
 
 from . import open_clip
 from .data import LQGTDataset
-from .metrics import image_metrics
+from .metrics import image_metrics, image_metrics_device
 from .models import create_model, parse_options
 from .preprocess import tensor2img
 from .sde import IRSDE
@@ -61,7 +64,9 @@ def resolve_crop_border(opt: dict, crop_border: Optional[int] = None) -> int:
 def evaluate(opt: dict, lq_dir: str, gt_dir: Optional[str], out_dir: str, batch: int = 8,
              device: str = "cuda", dtype: str = "fp32", synthetic: bool = False,
              clip_name: str = "daclip_ViT-B-32", crop_border: Optional[int] = None,
-             suffix: str = "") -> dict:
+             suffix: str = "", metrics: str = "host") -> dict:
+    if metrics not in ("host", "device"):
+        raise ValueError(f"metrics must be 'host' or 'device', got {metrics!r}")
     crop_border = resolve_crop_border(opt, crop_border)
     model, clip, sde, mode = _setup(opt, device, dtype, synthetic, clip_name)
     ds = LQGTDataset(lq_dir, gt_dir)
@@ -85,14 +90,19 @@ def evaluate(opt: dict, lq_dir: str, gt_dir: Optional[str], out_dir: str, batch:
             model.test(sde, mode=mode, save_states=False)
             torch.cuda.synchronize()
             times.append((time.time() - t0) / len(items))
-            vis = model.get_current_visuals(need_GT=gt_dir is not None)
+            if metrics == "device":
+                rows, outs_u8 = image_metrics_device(model.output, model.state_0 if gt_dir else None,
+                                                     crop_border)
+            else:
+                vis = model.get_current_visuals(need_GT=gt_dir is not None)
             for j, it in enumerate(items):
                 name = os.path.splitext(os.path.basename(it["GT_path"] or it["LQ_path"]))[0]
-                out_u8 = tensor2img(vis["Outputs"][j])                    # BGR HWC uint8
+                out_u8 = outs_u8[j] if metrics == "device" else tensor2img(vis["Outputs"][j])   # BGR HWC uint8
                 Image.fromarray(out_u8[:, :, ::-1]).save(os.path.join(out_dir, name + suffix + ".png"))
                 rec = {"time_s": times[-1]}
                 if gt_dir:
-                    rec.update(image_metrics(out_u8, tensor2img(vis["GTs"][j]), crop_border))
+                    rec.update(rows[j] if metrics == "device" else
+                               image_metrics(out_u8, tensor2img(vis["GTs"][j]), crop_border))
                     rec["lpips"] = None
                 per_image[name] = rec
     summary = {"images": len(per_image), "avg_time_s": float(np.mean(times)) if times else None}
@@ -116,9 +126,12 @@ def main(argv=None):
     ap.add_argument("--crop-border", type=int, default=None,
                     help="pixels cropped before the metrics (default: test.py:150, opt crop_border else "
                          "degradation.scale)")
+    ap.add_argument("--metrics", default="host", choices=["host", "device"],
+                    help="where the uint8 outputs and PSNR / SSIM are computed: host numpy (default) or the "
+                         "fp64 HIP kernels")
     a = ap.parse_args(argv)
     res = evaluate(parse_options(a.opt), a.lq, a.gt, a.out, a.batch, dtype=a.dtype, synthetic=a.synthetic,
-                   clip_name=a.clip, crop_border=a.crop_border)
+                   clip_name=a.clip, crop_border=a.crop_border, metrics=a.metrics)
     print(json.dumps(res["summary"]))
     return res
 

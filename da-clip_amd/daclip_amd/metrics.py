@@ -1,4 +1,6 @@
-"""Image-quality metrics of the reference evaluation (host-side numpy, like the reference).
+"""Image-quality metrics of the reference evaluation: host-side numpy like the reference
+(`image_metrics`, the yardstick), and the same numbers from the fp64 HIP kernels of
+csrc/metrics.hip for a batch that is still on the GPU (`image_metrics_device`).
 
 * calculate_psnr: utils/img_utils.py:182-189 (float64 MSE over all pixels, inf if equal).
 * ssim / calculate_ssim: utils/img_utils.py:192-234. Gaussian window 11x11, sigma 1.5 (the
@@ -86,3 +88,68 @@ def image_metrics(out_u8: np.ndarray, gt_u8: np.ndarray, crop_border: int = 0) -
         res["psnr_y"] = calculate_psnr(crop(sy, crop_border) * 255, crop(gy, crop_border) * 255)
         res["ssim_y"] = calculate_ssim(crop(sy, crop_border) * 255, crop(gy, crop_border) * 255)
     return res
+
+
+def image_metrics_records(out, gt, crop_border: int = 0):
+    """One dac_image_metrics call: (records, out_u8) for out, gt [B,C,H,W] float tensors on one
+    GPU. records is the [B, 8] float64 array {sse, n, ssim, sse_y, n_y, ssim_y, nonfinite, 0}
+    of include/daclip_hip.h, out_u8 the [B,H,W,C] uint8 BGR array. Scratch and results are
+    torch allocations on the inputs' device, the kernels run on its current stream."""
+    import torch
+
+    from . import _lib
+    if out.dim() != 4 or tuple(out.shape) != tuple(gt.shape):
+        raise ValueError(f"out and gt must be [B,C,H,W] of one shape, got {tuple(out.shape)} and {tuple(gt.shape)}")
+    B, C, H, W = (int(v) for v in out.shape)
+    L = _lib.lib()
+    ws_bytes = L.dac_image_metrics_workspace(B, C, H, W, int(crop_border))
+    if ws_bytes == 0:
+        raise ValueError(f"image metrics on the device: unsupported B={B} C={C} H={H} W={W} "
+                         f"crop_border={crop_border} (C in {{1, 3}}, cropped window >= 11x11)")
+    if not (out.is_cuda and gt.is_cuda and out.device == gt.device):
+        raise RuntimeError("image metrics on the device need out and gt on one GPU")
+    dev = out.device
+    with torch.cuda.device(dev):
+        o = out.detach().float().contiguous()
+        g = o if gt is out else gt.detach().float().contiguous()
+        o8 = torch.empty((B, H, W, C), dtype=torch.uint8, device=dev)
+        g8 = torch.empty((B, H, W, C), dtype=torch.uint8, device=dev)
+        res = torch.empty((B, 8), dtype=torch.float64, device=dev)
+        ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.float64, device=dev)
+        rc = L.dac_image_metrics(_lib._ptr(o), _lib._ptr(g), B, C, H, W, int(crop_border), _lib._ptr(o8),
+                                 _lib._ptr(g8), _lib._ptr(res), _lib._ptr(ws), _lib._stream(dev))
+        if rc == _lib.DAC_E_ARG:
+            raise ValueError(f"dac_image_metrics refused B={B} C={C} H={H} W={W} crop_border={crop_border}")
+        if rc != 0:
+            raise RuntimeError(f"dac_image_metrics failed ({rc})")
+        return res.cpu().numpy(), o8.cpu().numpy()
+
+
+def image_metrics_device(out, gt=None, crop_border: int = 0):
+    """`image_metrics` and `tensor2img` for a whole batch on the GPU (csrc/metrics.hip).
+
+    out, gt: [B,C,H,W] float tensors on one GPU, RGB, C in {1, 3}. Returns (rows, out_u8):
+    rows[i] has the keys of `image_metrics` for image i (psnr, ssim, and for C = 3 psnr_y,
+    ssim_y); out_u8 is the [B,H,W,C] uint8 numpy array, BGR, that `tensor2img` would give
+    per image. gt=None: only the uint8 images are wanted (out stands in as its own gt, with no
+    crop, and rows is None). ValueError: a shape the kernels refuse (unlike the host path, a
+    cropped window smaller than the 11x11 filter is an error, not NaN). RuntimeError: non-finite
+    inputs."""
+    score = gt is not None
+    r, out_u8 = image_metrics_records(out, gt if score else out, crop_border if score else 0)
+    if (r[:, 6] > 0).any():
+        bad = {i: int(r[i, 6]) for i in range(len(r)) if r[i, 6] > 0}
+        raise RuntimeError(f"non-finite values in the images to score (image: count) {bad}")
+    if not score:
+        return None, out_u8
+
+    def psnr(sse, n):
+        return float("inf") if sse == 0 else 20 * math.log10(255.0 / math.sqrt(sse / n))
+    rows = []
+    for rec in r:
+        row = {"psnr": psnr(rec[0], rec[1]), "ssim": float(rec[2])}
+        if out.shape[1] == 3:
+            row["psnr_y"] = psnr(rec[3], rec[4])
+            row["ssim_y"] = float(rec[5])
+        rows.append(row)
+    return rows, out_u8

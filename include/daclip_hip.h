@@ -202,6 +202,30 @@ enum { DAC_ATTN_Q_PRESCALED = 8 };
 int dac_op_attention(const void* qkv, void* out, int B, int L, int H, int dtype, int variant,
                      void* stream);
 
+/* Evaluation metrics of config/daclip-sde/test.py:131-196 on the device, handle-less (the
+ * caller owns all memory; everything on the current device). out / gt: fp32 [B,C,H,W] RGB,
+ * C in {1, 3}. out_bytes / gt_bytes: uint8 [B,H,W,C], BGR for C = 3, what util.tensor2img
+ * gives (clamp to [0,1], * 255 in fp32, round half to even); both are required, the metrics
+ * read them. A non-finite input is stored as 0 and counted. results: double [B][8] =
+ *   { sse, n, ssim, sse_y, n_y, ssim_y, nonfinite, reserved }
+ * over the window cropped by crop_border on every side: sse = exact sum of squared byte
+ * differences over all channels, n = its element count (PSNR = 20 log10(255 / sqrt(sse / n)),
+ * infinite for sse == 0); ssim = mean of every channel's SSIM map (11x11 Gaussian window,
+ * sigma 1.5, 'valid' region, C1 = (0.01*255)^2, C2 = (0.03*255)^2; utils/img_utils.py:192-234),
+ * fp64; the _y entries are the same on Y = (24.966 B + 128.553 G + 65.481 R) / 255 + 16, kept
+ * unrounded (data/util.py:189-210 on a float image), and 0 for C = 1; nonfinite = non-finite
+ * values among the image's out and gt inputs. A record depends on neither B, the image's
+ * place in the batch, nor the run (no atomics, fixed summation order).
+ * workspace: dac_image_metrics_workspace(...) bytes of device scratch, 8-byte aligned.
+ * DAC_E_ARG (before any device work): a null pointer, B < 1 (or > 16383), C not 1 or 3,
+ * crop_border < 0, or a cropped height or width below 11; dac_image_metrics_workspace returns
+ * 0 for the same shapes. The host metrics give NaN (with a numpy warning) for a window smaller
+ * than the filter; this entry point refuses it instead. */
+size_t dac_image_metrics_workspace(int B, int C, int H, int W, int crop_border);
+int dac_image_metrics(const float* out, const float* gt, int B, int C, int H, int W, int crop_border,
+                      unsigned char* out_bytes, unsigned char* gt_bytes, double* results,
+                      void* workspace, void* stream);
+
 const char* dac_last_error(dac_handle* h);
 
 /* Build provenance baked in at compile time: "<sha256 of the library sources>[:16] git=<HEAD>"

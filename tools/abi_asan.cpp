@@ -54,6 +54,17 @@ int main() {
   EXPECT(dac_op_attention(dummy, dummy, 1, 64, 1, 99, 0, nullptr) == DAC_E_ARG);      // bad dtype
   EXPECT(dac_op_attention(dummy, dummy, 1, 100, 1, DAC_F32, 2, nullptr) == DAC_E_ARG); // variant 2: fp32
   EXPECT(dac_op_attention(dummy, dummy, 1, 2048, 1, DAC_BF16, 3, nullptr) == DAC_E_ARG); // L > 1024
+  // dac_image_metrics: null pointers and unsupported shapes are refused before any device work.
+  unsigned char bytes[4] = {0, 0, 0, 0};
+  double rec[8];
+  EXPECT(dac_image_metrics(nullptr, nullptr, 1, 3, 11, 11, 0, nullptr, nullptr, nullptr, nullptr, nullptr) == DAC_E_ARG);
+  EXPECT(dac_image_metrics(dummy, dummy, 1, 3, 11, 11, 0, bytes, bytes, rec, nullptr, nullptr) == DAC_E_ARG);
+  EXPECT(dac_image_metrics(dummy, dummy, 0, 3, 11, 11, 0, bytes, bytes, rec, rec, nullptr) == DAC_E_ARG);   // B
+  EXPECT(dac_image_metrics(dummy, dummy, 1, 2, 11, 11, 0, bytes, bytes, rec, rec, nullptr) == DAC_E_ARG);   // C
+  EXPECT(dac_image_metrics(dummy, dummy, 1, 3, 10, 11, 0, bytes, bytes, rec, rec, nullptr) == DAC_E_ARG);   // H < 11
+  EXPECT(dac_image_metrics(dummy, dummy, 1, 3, 16, 16, 3, bytes, bytes, rec, rec, nullptr) == DAC_E_ARG);   // cropped 10
+  EXPECT(dac_image_metrics(dummy, dummy, 1, 3, 16, 16, -1, bytes, bytes, rec, rec, nullptr) == DAC_E_ARG);
+  EXPECT(dac_image_metrics_workspace(1, 3, 11, 11, 0) > 0 && dac_image_metrics_workspace(1, 3, 10, 11, 0) == 0);
   std::printf("build: %s\n", dac_build_id());
 
   // Unsupported UNet configurations fail in dac_create, and the half-built handle is freed.
