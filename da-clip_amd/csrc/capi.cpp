@@ -242,6 +242,47 @@ int dac_sde_reverse(dac_handle* h, int mode, float* x_inout, const float* mu, co
   });
 }
 
+int dac_sde_reverse_tiled(dac_handle* h, int mode, float* x_inout, const float* mu,
+                          const float* text_ctx, const float* image_ctx, int B, int H, int W, int th,
+                          int tw, int overlap, const int32_t* ys, int ny, const int32_t* xs, int nx,
+                          int tiles_per_forward, int T, const float* noise, uint64_t seed,
+                          void* stream) {
+  return guard(h, [&]() -> int {
+    // Every argument check comes before the first device call.
+    if (!x_inout || !mu || (mode != DAC_POSTERIOR && mode != DAC_SDE))
+      throw dac::Error(DAC_E_ARG, "bad argument");
+    const dac::TileGrid g = dac::check_tile_grid(B, H, W, th, tw, overlap, ys, ny, xs, nx);
+    if (tiles_per_forward < 1) throw dac::Error(DAC_E_ARG, "tiles_per_forward must be >= 1");
+    need_ready(h);
+    h->eng->sde_reverse_tiled(mode, x_inout, mu, text_ctx, image_ctx, B, H, W, g, tiles_per_forward, T,
+                              noise, seed, (hipStream_t)stream);
+    return DAC_OK;
+  });
+}
+
+int dac_op_tile_blend(const float* eps_tiles, float* eps_full, int B, int H, int W, int th, int tw,
+                      int overlap, const int32_t* ys, int ny, const int32_t* xs, int nx,
+                      void* stream) {
+  if (!eps_tiles || !eps_full) return DAC_E_ARG;
+  try {
+    (void)dac::check_tile_grid(B, H, W, th, tw, overlap, ys, ny, xs, nx);
+  } catch (const std::exception&) {
+    return DAC_E_ARG;
+  }
+  const hipStream_t st = (hipStream_t)stream;
+  int32_t* dev = nullptr;
+  if (hipMalloc(&dev, (size_t)(ny + nx) * sizeof(int32_t)) != hipSuccess) return DAC_E_NOMEM;
+  hipError_t e = hipMemcpyAsync(dev, ys, ny * sizeof(int32_t), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(dev + ny, xs, nx * sizeof(int32_t), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) {
+    dac::tile_blend(eps_tiles, eps_full, dev, dev + ny, xs, B, ny, nx, H, W, th, tw, overlap, st);
+    e = hipGetLastError();
+  }
+  const hipError_t es = hipStreamSynchronize(st);
+  (void)hipFree(dev);
+  return e == hipSuccess && es == hipSuccess ? DAC_OK : DAC_E_HIP;
+}
+
 int dac_set_noise_offset(dac_handle* h, uint64_t first_image) {
   return guard(h, [&]() -> int {
     h->eng->set_noise_offset(first_image);

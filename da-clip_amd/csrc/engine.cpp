@@ -742,6 +742,33 @@ static void ln(Run& r, const void* x, int ldx, void* y, int ldy, const void* res
 }
 
 // ============================================================================= schedule
+TileGrid check_tile_grid(int B, int H, int W, int th, int tw, int overlap, const int32_t* ys, int ny,
+                         const int32_t* xs, int nx) {
+  auto bad = [](const std::string& m) { throw Error(DAC_E_ARG, "tile grid: " + m); };
+  if (B < 1 || H < 2 || W < 2) bad("needs B >= 1 and an image of at least 2 x 2");
+  if (!ys || !xs || ny < 1 || nx < 1) bad("null or empty offset list");
+  if (th < 2 || tw < 2) bad("tile sides must be >= 2");
+  if (th > H || tw > W) bad("tile larger than the image (clamp it to the image size)");
+  if (overlap < 0 || overlap >= std::min(th, tw)) bad("overlap must be in [0, min(th, tw))");
+  auto axis = [&](const int32_t* o, int n, int l, int L, const char* name) {
+    for (int i = 0; i < n; ++i) {
+      if (o[i] < 0 || o[i] > L - l) bad(std::string(name) + " offset out of bounds");
+      if (i && o[i] <= o[i - 1]) bad(std::string(name) + " offsets must ascend");
+      if (i && o[i] > o[i - 1] + l) bad(std::string(name) + " axis has a gap between tiles");
+    }
+    if (o[0] != 0 || o[n - 1] != L - l) bad(std::string(name) + " axis is not covered to its ends");
+  };
+  axis(ys, ny, th, H, "row");
+  axis(xs, nx, tw, W, "column");
+  if ((long long)B * ny * nx > (1 << 20) || (long long)B * H * W > INT32_MAX / 4)
+    bad("too many tiles or pixels for one call");
+  TileGrid g;
+  g.th = th; g.tw = tw; g.ov = overlap;
+  g.ys.assign(ys, ys + ny);
+  g.xs.assign(xs, xs + nx);
+  return g;
+}
+
 void compute_schedule(SdeSchedule& s, float max_sigma, int T, int schedule, float eps) {
   // sde_utils.py:84-154 in fp32 (torch 0-dim / 1-D float32 semantics).
   const double ms = max_sigma >= 1 ? max_sigma / 255.0 : max_sigma;
@@ -1820,6 +1847,7 @@ class EngineT : public Engine {
     clear_graphs();
     if (arena.base) (void)hipFree(arena.base);
     for (auto& kv : bufs) free_bufs(kv.second);
+    for (auto& kv : tloops) free_tbufs(kv.second.b);
     (void)hipEventDestroy(ev_in);
     (void)hipEventDestroy(ev_out);
     (void)hipEventDestroy(ev_fork);
@@ -2022,6 +2050,11 @@ class EngineT : public Engine {
   void clear_graphs() {
     for (auto& kv : graphs) (void)hipGraphExecDestroy(kv.second);
     graphs.clear();
+    for (auto& kv : tloops) {
+      for (auto& g : kv.second.graphs)
+        if (g.second) (void)hipGraphExecDestroy(g.second);
+      kv.second.graphs.clear();
+    }
   }
   void record_loop(Run& r, Bufs& b, int mode, int B, int H, int W, int nT, bool has_noise,
                    bool has_tc, bool has_ic) {
@@ -2120,6 +2153,211 @@ class EngineT : public Engine {
         it = graphs.emplace(key, ex).first;
       }
       HIP_OK(hipGraphLaunch(it->second, priv));
+    }
+    HIP_OK(hipMemcpyAsync(x, b.xs, n * 4, hipMemcpyDeviceToDevice, priv));
+    HIP_OK(hipEventRecord(ev_out, priv));
+    HIP_OK(hipStreamWaitEvent(st, ev_out, 0));
+  }
+
+  // ------------------------------------------------------------------ tiled loop
+  // One full-image state; every step gathers its tiles, runs the UNet on them C at a time,
+  // blends the per-tile eps back to a full-image eps (tile.hip) and applies the flat fp32 sampler
+  // update to the whole image, so the noise and the trajectory do not depend on the tiling.
+  // Buffers and graphs are cached per (shape, grid contents, chunk, T); the buffers live outside
+  // the arena (the arena only holds one forward's activations).
+  struct TKey {
+    int B, H, W, th, tw, ov, C, nT;
+    std::vector<int32_t> ys, xs;
+    bool operator<(const TKey& o) const {
+      return std::tie(B, H, W, th, tw, ov, C, nT, ys, xs) <
+             std::tie(o.B, o.H, o.W, o.th, o.tw, o.ov, o.C, o.nT, o.ys, o.xs);
+    }
+  };
+  struct TBufs {
+    float *xs = nullptr, *mus = nullptr, *tcs = nullptr, *ics = nullptr, *ss = nullptr, *cc = nullptr,
+          *sin = nullptr, *noise = nullptr;
+    float *xt = nullptr;          // [C, 3, th, tw] tiles of the current state (one chunk)
+    float *mut = nullptr;         // [NT, 3, th, tw] tiles of mu, gathered once per call
+    float *epst = nullptr;        // [NT, 3, th, tw] per-tile eps
+    float *eps = nullptr;         // [B, 3, H, W] blended eps
+    float *ssc = nullptr;         // [C, ss_total] the chunk's (scale, shift) rows
+    float *cct = nullptr;         // [NT, cc_total] cross-attention constants per tile
+    int32_t *ysd = nullptr, *xsd = nullptr;
+    void* out = nullptr;
+    uint64_t* seed = nullptr;
+    int ldo = 0;
+  };
+  struct TLoop {
+    TBufs b;
+    std::map<int, hipGraphExec_t> graphs;     // by mode | feature bits; null = runs eagerly
+  };
+  std::map<TKey, TLoop> tloops;
+  static constexpr size_t kMaxTiledShapes = 4;
+  // A captured loop with more nodes than this is not instantiated: the loop is enqueued eagerly
+  // on the private stream instead (the same launch sequence, so the same result).
+  static constexpr size_t kMaxGraphNodes = 65536;
+  void free_tbufs(TBufs& b) {
+    for (void* p : {(void*)b.xs, (void*)b.mus, (void*)b.tcs, (void*)b.ics, (void*)b.ss, (void*)b.cc,
+                    (void*)b.sin, (void*)b.noise, (void*)b.xt, (void*)b.mut, (void*)b.epst, (void*)b.eps,
+                    (void*)b.ssc, (void*)b.cct, (void*)b.ysd, (void*)b.xsd, b.out, (void*)b.seed})
+      if (p) (void)hipFree(p);
+    b = TBufs();
+  }
+  TLoop& get_tloop(const TKey& key) {
+    auto it = tloops.find(key);
+    if (it != tloops.end()) return it->second;
+    if (tloops.size() >= kMaxTiledShapes) {
+      HIP_OK(hipDeviceSynchronize());
+      clear_graphs();
+      for (auto& kv : tloops) free_tbufs(kv.second.b);
+      tloops.clear();
+    }
+    TLoop& L = tloops[key];
+    TBufs& b = L.b;
+    try {
+      const int ny = (int)key.ys.size(), nx = (int)key.xs.size(), NT = key.B * ny * nx;
+      const size_t n = (size_t)key.B * 3 * key.H * key.W, tn = (size_t)3 * key.th * key.tw;
+      const int Hp = unet->pad_of(key.th), Wp = unet->pad_of(key.tw);
+      b.xs = dalloc<float>(n);
+      b.mus = dalloc<float>(n);
+      b.eps = dalloc<float>(n);
+      b.tcs = dalloc<float>((size_t)key.B * std::max(1, unet->ctx));
+      b.ics = dalloc<float>((size_t)key.B * std::max(1, unet->ctx));
+      b.ss = dalloc<float>((size_t)key.nT * key.B * unet->ss_total);
+      b.cc = dalloc<float>((size_t)key.B * std::max(1, unet->cc_total));
+      b.sin = dalloc<float>((size_t)key.nT * key.B * unet->nf);
+      b.xt = dalloc<float>((size_t)key.C * tn);
+      b.mut = dalloc<float>((size_t)NT * tn);
+      b.epst = dalloc<float>((size_t)NT * tn);
+      b.ssc = dalloc<float>((size_t)key.C * unet->ss_total);
+      b.cct = dalloc<float>((size_t)NT * std::max(1, unet->cc_total));
+      b.ldo = 4;
+      b.out = dalloc<char>((size_t)key.C * Hp * Wp * b.ldo * sizeof(T));
+      b.seed = dalloc<uint64_t>(2);
+      b.ysd = dalloc<int32_t>(ny);
+      b.xsd = dalloc<int32_t>(nx);
+      HIP_OK(hipMemcpy(b.ysd, key.ys.data(), ny * sizeof(int32_t), hipMemcpyHostToDevice));
+      HIP_OK(hipMemcpy(b.xsd, key.xs.data(), nx * sizeof(int32_t), hipMemcpyHostToDevice));
+    } catch (...) {
+      free_tbufs(b);
+      tloops.erase(key);
+      throw;
+    }
+    return L;
+  }
+  // Arena bytes of the tiled loop: the tables of the B images, one forward of a full chunk and
+  // one of the ragged last chunk (dry runs; they also carry the forward's argument checks).
+  size_t plan_tiled(int B, int C, int rag, int th, int tw, int nT, bool has_ic) {
+    Arena a;
+    a.dry = true;
+    Run r;
+    r.dry = true;
+    r.ar = &a;
+    set_side(r);
+    const float* dummy = (const float*)1;
+    unet->tables(r, nullptr, nT, 0.0, 0.0, 1.0, dummy, has_ic ? dummy : nullptr, B, nullptr, nullptr);
+    for (int nb : {C, rag}) {
+      if (nb < 1) continue;
+      a.reset();
+      unet->forward(r, nullptr, nullptr, nb, th, tw, nullptr, has_ic ? dummy : nullptr, nullptr, 4);
+    }
+    return a.peak + (1 << 20);
+  }
+  void record_tiled(Run& r, TBufs& b, const TKey& k, int mode, bool has_noise, bool has_tc, bool has_ic) {
+    const int ny = (int)k.ys.size(), nx = (int)k.xs.size(), per = ny * nx, NT = k.B * per;
+    const int Hp = unet->pad_of(k.th), Wp = unet->pad_of(k.tw);
+    const size_t n = (size_t)k.B * 3 * k.H * k.W, tn = (size_t)3 * k.th * k.tw;
+    r.ar->reset();
+    // Per-image tables (step i runs the model at (T - i) * sample_scale); a chunk's rows are
+    // copies of its tiles' images' rows.
+    unet->tables(r, b.sin, k.nT, (double)k.nT, -1.0, sched.time_scale, has_tc ? b.tcs : nullptr,
+                 has_ic ? b.ics : nullptr, k.B, b.ss, b.cc);
+    if (!r.dry) {
+      tile_gather(b.mus, b.mut, b.ysd, b.xsd, k.xs.data(), ny, nx, k.H, k.W, k.th, k.tw, 0, NT, r.st);
+      if (has_ic) rows_gather(b.cc, b.cct, NT, unet->cc_total, 0, per, r.st);
+    }
+    for (int i = 0; i < k.nT; ++i) {
+      const int t = k.nT - i;
+      for (int k0 = 0; k0 < NT; k0 += k.C) {
+        const int nb = std::min(k.C, NT - k0);
+        r.ar->reset();
+        if (!r.dry) {
+          tile_gather(b.xs, b.xt, b.ysd, b.xsd, k.xs.data(), ny, nx, k.H, k.W, k.th, k.tw, k0, nb, r.st);
+          rows_gather(b.ss + (size_t)i * k.B * unet->ss_total, b.ssc, nb, unet->ss_total, k0, per, r.st);
+        }
+        unet->forward(r, b.xt, b.mut + (size_t)k0 * tn, nb, k.th, k.tw, b.ssc,
+                      has_ic ? b.cct + (size_t)k0 * unet->cc_total : nullptr, b.out, b.ldo);
+        if (!r.dry) unet_out<T>(b.out, b.ldo, b.epst + (size_t)k0 * tn, nb, k.th, k.tw, Hp, Wp, r.st);
+      }
+      if (!r.dry) {
+        tile_blend(b.epst, b.eps, b.ysd, b.xsd, k.xs.data(), k.B, ny, nx, k.H, k.W, k.th, k.tw, k.ov, r.st);
+        // The flat fp32 sampler update on the full image (eps is NCHW: ld = 0).
+        sde_step<float>(mode, b.xs, b.mus, b.eps, 0, 1, 1, has_noise ? b.noise + (size_t)i * n : nullptr,
+                        b.seed, (uint32_t)t, sched.coef(t, mode), 1, 1, (int)(n / 3), r.st);
+      }
+    }
+  }
+  void sde_reverse_tiled(int mode, float* x, const float* mu, const float* tc, const float* icx, int B,
+                         int H, int W, const TileGrid& g, int tpf, int nT, const float* noise,
+                         uint64_t seed, hipStream_t st) override {
+    need(unet != nullptr, "handle has no UNet");
+    need(tpf >= 1, "tiles_per_forward must be >= 1");
+    need(sched.T > 0, "call dac_sde_schedule first");
+    need(nT >= 1 && nT <= sched.T, "T exceeds the schedule length");
+    if (prof.kernel_id >= 0)
+      throw Error(DAC_E_STATE, "the tiled loop has no profiling mode (disable profiling first)");
+    HIP_OK(hipSetDevice(dev));
+    const bool has_tc = tc != nullptr && unet->degra;
+    const bool has_ic = icx != nullptr && unet->imgctx;
+    const bool has_noise = noise != nullptr;
+    const int NT = B * (int)g.ys.size() * (int)g.xs.size();
+    const int C = std::min(tpf, NT);
+    ensure_arena(plan_tiled(B, C, NT % C, g.th, g.tw, nT, has_ic));
+    const TKey key{B, H, W, g.th, g.tw, g.ov, C, nT, g.ys, g.xs};
+    TLoop& L = get_tloop(key);
+    TBufs& b = L.b;
+    const size_t n = (size_t)B * 3 * H * W;
+    if (has_noise && !b.noise) b.noise = dalloc<float>((size_t)nT * n);
+    HIP_OK(hipEventRecord(ev_in, st));
+    HIP_OK(hipStreamWaitEvent(priv, ev_in, 0));
+    HIP_OK(hipMemcpyAsync(b.xs, x, n * 4, hipMemcpyDeviceToDevice, priv));
+    HIP_OK(hipMemcpyAsync(b.mus, mu, n * 4, hipMemcpyDeviceToDevice, priv));
+    if (has_tc) HIP_OK(hipMemcpyAsync(b.tcs, tc, (size_t)B * unet->ctx * 4, hipMemcpyDeviceToDevice, priv));
+    if (has_ic) HIP_OK(hipMemcpyAsync(b.ics, icx, (size_t)B * unet->ctx * 4, hipMemcpyDeviceToDevice, priv));
+    if (has_noise) HIP_OK(hipMemcpyAsync(b.noise, noise, (size_t)nT * n * 4, hipMemcpyDeviceToDevice, priv));
+    // The noise key of the untiled loop: a pixel's draw depends on the full image alone.
+    set_u64x2(b.seed, seed, noise_offset * (uint64_t)(3 * H * W), priv);
+    const int mkey = mode | (has_tc ? 0 : 2) | (has_ic ? 0 : 4) | (has_noise ? 8 : 0);
+    static const bool no_graph = getenv("DAC_NO_GRAPH") && getenv("DAC_NO_GRAPH")[0] == '1';
+    auto it = L.graphs.find(mkey);
+    if (it == L.graphs.end() && !no_graph) {
+      Run r = live(priv);
+      hipGraph_t gr = nullptr;
+      HIP_OK(hipStreamBeginCapture(priv, hipStreamCaptureModeThreadLocal));
+      try {
+        record_tiled(r, b, key, mode, has_noise, has_tc, has_ic);
+      } catch (...) {
+        hipGraph_t dead = nullptr;
+        (void)hipStreamEndCapture(priv, &dead);
+        if (dead) (void)hipGraphDestroy(dead);
+        throw;
+      }
+      HIP_OK(hipStreamEndCapture(priv, &gr));
+      size_t nn = 0;
+      hipError_t e = hipGraphGetNodes(gr, nullptr, &nn);
+      hipGraphExec_t ex = nullptr;
+      // DAC_TILED_MAX_NODES: the limit for this call (tests compare the two forms).
+      const char* lim = getenv("DAC_TILED_MAX_NODES");
+      if (e == hipSuccess && nn <= (lim ? (size_t)atoll(lim) : kMaxGraphNodes)) e = hipGraphInstantiate(&ex, gr, nullptr, nullptr, 0);
+      (void)hipGraphDestroy(gr);
+      HIP_OK(e);
+      it = L.graphs.emplace(mkey, ex).first;
+    }
+    if (it != L.graphs.end() && it->second) {
+      HIP_OK(hipGraphLaunch(it->second, priv));
+    } else {
+      Run r = live(priv);
+      record_tiled(r, b, key, mode, has_noise, has_tc, has_ic);
     }
     HIP_OK(hipMemcpyAsync(x, b.xs, n * 4, hipMemcpyDeviceToDevice, priv));
     HIP_OK(hipEventRecord(ev_out, priv));

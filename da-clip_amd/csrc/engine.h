@@ -198,9 +198,24 @@ struct SdeSchedule {
 };
 void compute_schedule(SdeSchedule& s, float max_sigma, int T, int schedule, float eps);
 
+// Tile grid of the tiled restore loop: tiles of th x tw at the product of the row offsets ys
+// and the column offsets xs, blended with the ramp weight min(i + 1, l - i, ov + 1) per axis.
+struct TileGrid {
+  int th = 0, tw = 0, ov = 0;
+  std::vector<int32_t> ys, xs;
+};
+// Host-only checks of a grid over B images of H x W (throws DAC_E_ARG): sizes, overlap, offsets
+// ascending and in bounds, every row and column covered.
+TileGrid check_tile_grid(int B, int H, int W, int th, int tw, int overlap, const int32_t* ys, int ny,
+                         const int32_t* xs, int nx);
+
 class Engine {
  public:
   virtual ~Engine() = default;
+  virtual void sde_reverse_tiled(int mode, float* x, const float* mu, const float* tc,
+                                 const float* icx, int B, int H, int W, const TileGrid& g,
+                                 int tiles_per_forward, int T, const float* noise, uint64_t seed,
+                                 hipStream_t st) = 0;
   virtual void finalize(WStore& w) = 0;
   virtual void encode(const float* img, int B, float* ic, float* dc, hipStream_t st) = 0;
   virtual void encode_text(const int64_t* tokens, int N, float* out, hipStream_t st) = 0;

@@ -318,6 +318,23 @@ void sde_step(int mode, float* x, const float* mu, const void* eps, int ld, int 
 // Whether sde_step can take xin for this layout (the per-pixel kernel on unpadded images).
 bool sde_step_fuses(int ld, int H, int W, int Hp, int Wp);
 
+// Tiled restoration (tile.hip). The tile grid is separable: row offsets ys[ny], column offsets
+// xs[nx] (device copies for the kernels, the host xs to choose the 16-byte path), tiles of
+// th x tw; tile k = (b*ny + iy)*nx + ix.
+// dst[j, c, y, x] = src[b, c, ys[iy] + y, xs[ix] + x] for the nk tiles k = k0 + j; src is
+// [B, 3, H, W], dst [nk, 3, th, tw], both NCHW fp32.
+void tile_gather(const float* src, float* dst, const int32_t* ys_dev, const int32_t* xs_dev,
+                 const int32_t* xs_host, int ny, int nx, int H, int W, int th, int tw, int k0, int nk,
+                 hipStream_t st);
+// tiles [B*ny*nx, 3, th, tw] -> out [B, 3, H, W]: a pixel inside one tile is copied; otherwise
+// (sum_k w_k * tile_k) / (sum_k w_k), k ascending, w = wy * wx with the per-axis ramp
+// min(i + 1, l - i, ov + 1); fp32, multiply and add rounded separately, one division.
+void tile_blend(const float* tiles, float* out, const int32_t* ys_dev, const int32_t* xs_dev,
+                const int32_t* xs_host, int B, int ny, int nx, int H, int W, int th, int tw, int ov,
+                hipStream_t st);
+// dst[j, :ld] = src[(k0 + j) / per, :ld] for j < rows (per-image rows repeated per tile).
+void rows_gather(const float* src, float* dst, int rows, int ld, int k0, int per, hipStream_t st);
+
 // ViT input: NCHW fp32 image -> NHWC T with channels padded to VE.
 template <typename T>
 void vit_prep(const float* img, void* x, int B, int S, hipStream_t st);

@@ -30,6 +30,7 @@ DAC_SRC_F32, DAC_SRC_F16, DAC_SRC_BF16 = 0, 1, 2
 DAC_POSTERIOR, DAC_SDE = 0, 1
 DAC_COSINE, DAC_LINEAR, DAC_CONSTANT = 0, 1, 2
 DAC_E_MISSING, DAC_E_KEY, DAC_E_ARG = -3, -2, -1
+DAC_E_STATE = -4
 DAC_ATTN_Q_PRESCALED = 8
 
 EXPORTS = ["dac_create", "dac_destroy", "dac_set_weight", "dac_finalize_weights",
@@ -37,7 +38,8 @@ EXPORTS = ["dac_create", "dac_destroy", "dac_set_weight", "dac_finalize_weights"
            "dac_sde_schedule", "dac_sde_set_time_scale", "dac_sde_reverse", "dac_build_id",
            "dac_set_noise_offset", "dac_posterior_step", "dac_unet_flops", "dac_encode_flops", "dac_profile_enable",
            "dac_profile_read", "dac_profile_mode", "dac_profile_launch", "dac_profile_graph_ms",
-           "dac_op_attention", "dac_image_metrics_workspace", "dac_image_metrics", "dac_last_error"]
+           "dac_op_attention", "dac_image_metrics_workspace", "dac_image_metrics", "dac_last_error",
+           "dac_sde_reverse_tiled", "dac_op_tile_blend"]
 
 
 class DacConfig(ctypes.Structure):
@@ -65,6 +67,7 @@ def lib() -> ctypes.CDLL:
                           f"g.build()'` (or `make -C da-clip_amd`)")
     L = ctypes.CDLL(LIB_PATH)
     P, I, F, D, U64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_uint64
+    P32 = ctypes.POINTER(ctypes.c_int32)
     sig = {
         "dac_create": (I, [I, I, ctypes.POINTER(DacConfig), ctypes.POINTER(P)]),
         "dac_destroy": (None, [P]),
@@ -77,6 +80,8 @@ def lib() -> ctypes.CDLL:
         "dac_sde_schedule": (I, [P, F, I, I, F, P, F]),
         "dac_sde_set_time_scale": (I, [P, D]),
         "dac_sde_reverse": (I, [P, I, P, P, P, P, I, I, I, I, P, U64, P]),
+        "dac_sde_reverse_tiled": (I, [P, I, P, P, P, P, I, I, I, I, I, I, P32, I, P32, I, I, I, P, U64, P]),
+        "dac_op_tile_blend": (I, [P, P, I, I, I, I, I, I, P32, I, P32, I, P]),
         "dac_build_id": (ctypes.c_char_p, []),
         "dac_set_noise_offset": (I, [P, U64]),
         "dac_posterior_step": (I, [P, I, P, P, P, P, I, I, P]),

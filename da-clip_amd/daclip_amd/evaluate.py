@@ -4,6 +4,7 @@ per batch; images are independent, so per-image results do not depend on the gro
 
     python -m daclip_amd.evaluate --opt test.yml --lq LQ_DIR [--gt GT_DIR] --out OUT_DIR
                                   [--synthetic] [--batch 8] [--dtype bf16] [--metrics device]
+                                  [--tile 256 --tile-overlap 32]
 
 Per image: restored PNG (test.py:131-138) and, with GT, PSNR / SSIM / PSNR_Y / SSIM_Y
 (test.py:146-196). LPIPS needs its pretrained network, which is unavailable offline: not
@@ -11,6 +12,8 @@ computed (reported as None). --metrics host (default) quantises and scores on th
 (tensor2img + metrics.image_metrics); --metrics device does both in one fp64 HIP call per
 batch (metrics.image_metrics_device) and copies back only the uint8 images and the records;
 it refuses images whose cropped window is under 11x11 (the host path reports NaN there).
+--tile N restores every image tile by tile (N x N tiles, --tile-overlap pixels shared, blended at
+every sampler step): the way to restore photographs far larger than the 256 x 256 training crops.
 """
 from __future__ import annotations
 
@@ -64,7 +67,8 @@ def resolve_crop_border(opt: dict, crop_border: Optional[int] = None) -> int:
 def evaluate(opt: dict, lq_dir: str, gt_dir: Optional[str], out_dir: str, batch: int = 8,
              device: str = "cuda", dtype: str = "fp32", synthetic: bool = False,
              clip_name: str = "daclip_ViT-B-32", crop_border: Optional[int] = None,
-             suffix: str = "", metrics: str = "host") -> dict:
+             suffix: str = "", metrics: str = "host", tile=None, tile_overlap: int = 32,
+             tiles_per_forward: int = 16) -> dict:
     if metrics not in ("host", "device"):
         raise ValueError(f"metrics must be 'host' or 'device', got {metrics!r}")
     crop_border = resolve_crop_border(opt, crop_border)
@@ -87,7 +91,8 @@ def evaluate(opt: dict, lq_dir: str, gt_dir: Optional[str], out_dir: str, batch:
             model.feed_data(noisy, lq, gt, text_context=dc.float(), image_context=ic.float())
             torch.cuda.synchronize()
             t0 = time.time()
-            model.test(sde, mode=mode, save_states=False)
+            model.test(sde, mode=mode, save_states=False, tile=tile, tile_overlap=tile_overlap,
+                       tiles_per_forward=tiles_per_forward)
             torch.cuda.synchronize()
             times.append((time.time() - t0) / len(items))
             if metrics == "device":
@@ -129,9 +134,13 @@ def main(argv=None):
     ap.add_argument("--metrics", default="host", choices=["host", "device"],
                     help="where the uint8 outputs and PSNR / SSIM are computed: host numpy (default) or the "
                          "fp64 HIP kernels")
+    ap.add_argument("--tile", type=int, default=None,
+                    help="restore tile by tile with N x N tiles, blended at every sampler step (large images)")
+    ap.add_argument("--tile-overlap", type=int, default=32, help="pixels neighbouring tiles share")
     a = ap.parse_args(argv)
     res = evaluate(parse_options(a.opt), a.lq, a.gt, a.out, a.batch, dtype=a.dtype, synthetic=a.synthetic,
-                   clip_name=a.clip, crop_border=a.crop_border, metrics=a.metrics)
+                   clip_name=a.clip, crop_border=a.crop_border, metrics=a.metrics, tile=a.tile,
+                   tile_overlap=a.tile_overlap)
     print(json.dumps(res["summary"]))
     return res
 

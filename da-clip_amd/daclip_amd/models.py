@@ -78,19 +78,23 @@ class DenoisingModel:
         self.text_context = text_context
         self.image_context = image_context
 
-    def test(self, sde=None, mode="posterior", save_states=False, noises=None):
+    def test(self, sde=None, mode="posterior", save_states=False, noises=None, tile=None,
+             tile_overlap=32, tiles_per_forward=16):
         """denoising_model.py:152-162. `noises` ([T,B,C,H,W], optional) replaces the sampler's
-        per-step randn_like draws (parity tests inject the reference's noise)."""
+        per-step randn_like draws (parity tests inject the reference's noise). `tile` (int or
+        (th, tw)) restores tile by tile, blended at every step (IRSDE.reverse_posterior)."""
         sde.set_mu(self.condition)
+        tiled = {} if tile is None else dict(tile=tile, tile_overlap=tile_overlap,
+                                             tiles_per_forward=tiles_per_forward)
         with torch.no_grad():
             if mode == "sde":
                 self.output = sde.reverse_sde(self.state, save_states=save_states, noises=noises,
                                               text_context=self.text_context,
-                                              image_context=self.image_context)
+                                              image_context=self.image_context, **tiled)
             elif mode == "posterior":
                 self.output = sde.reverse_posterior(self.state, save_states=save_states, noises=noises,
                                                     text_context=self.text_context,
-                                                    image_context=self.image_context)
+                                                    image_context=self.image_context, **tiled)
             else:
                 raise ValueError(f"unknown sampling mode {mode}")
 

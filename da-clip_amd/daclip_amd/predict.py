@@ -61,15 +61,19 @@ class Predictor:
         return ic.float(), dc.float()
 
     def predict_batch(self, images_bgr: Sequence[np.ndarray], noise: Optional[torch.Tensor] = None,
-                      noises: Optional[torch.Tensor] = None) -> List[np.ndarray]:
+                      noises: Optional[torch.Tensor] = None, tile=None, tile_overlap: int = 32,
+                      tiles_per_forward: int = 16) -> List[np.ndarray]:
         """predict.py:62-91 for B same-size images. `noise` [B,3,H,W] / `noises` [T,B,3,H,W]
-        optionally replace the noise_state and per-step randn_like draws."""
+        optionally replace the noise_state and per-step randn_like draws. `tile` (int or
+        (th, tw)) restores large images tile by tile, blended at every sampler step; the CLIP
+        contexts stay one encode of the whole (resized) image."""
         rgb = [im[:, :, [2, 1, 0]] / 255.0 for im in images_bgr]
         ic, dc = self._contexts(rgb)
         lq = torch.stack([torch.tensor(im, dtype=torch.float32).permute(2, 0, 1) for im in rgb])
         noisy = self.sde.noise_state(lq, noise=noise)
         self.model.feed_data(noisy, lq, text_context=dc, image_context=ic)
-        self.model.test(self.sde, mode=self.mode, noises=noises)
+        self.model.test(self.sde, mode=self.mode, noises=noises, tile=tile, tile_overlap=tile_overlap,
+                        tiles_per_forward=tiles_per_forward)
         out = self.model.get_current_visuals(need_GT=False)["Outputs"]
         if not torch.isfinite(out).all():
             # 16-bit storage (fp16 saturates at 65504) must never turn into silent garbage pixels.
@@ -77,7 +81,9 @@ class Predictor:
         return [tensor2img(o) for o in out]
 
     def predict(self, image: Union[str, np.ndarray], noise: Optional[torch.Tensor] = None,
-                noises: Optional[torch.Tensor] = None) -> np.ndarray:
+                noises: Optional[torch.Tensor] = None, tile=None, tile_overlap: int = 32,
+                tiles_per_forward: int = 16) -> np.ndarray:
         """One image (path or BGR uint8 HWC) -> restored BGR uint8 HWC."""
         im = imread_bgr(image) if isinstance(image, str) else image
-        return self.predict_batch([im], noise=noise, noises=noises)[0]
+        return self.predict_batch([im], noise=noise, noises=noises, tile=tile, tile_overlap=tile_overlap,
+                                  tiles_per_forward=tiles_per_forward)[0]

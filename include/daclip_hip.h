@@ -143,6 +143,39 @@ int dac_sde_reverse(dac_handle* h, int mode, float* x_inout, const float* mu,
                     const float* text_ctx, const float* image_ctx, int B, int H, int W, int T,
                     const float* noise, uint64_t seed, void* stream);
 
+/* Tiled reverse loop for images larger than the network's training size: one full-image state
+ * x_inout [B,3,H,W]; at every step t = T..1 the tiles of x (th x tw windows at the product of
+ * the host offset lists ys[ny] x xs[nx], tile k = (b*ny + iy)*nx + ix) go through the UNet
+ * tiles_per_forward at a time (each with the context rows of its image; a tile whose side is
+ * not a multiple of the padding unit is reflect-padded like a stand-alone image), the per-tile
+ * eps are blended to a full-image eps and the sampler update of dac_sde_reverse acts on the full
+ * image with the full-image noise (injected [T,B,3,H,W], or Philox keyed by the full-image
+ * element under the dac_set_noise_offset rule), so a pixel's noise does not depend on the tiling.
+ * Blend: a pixel inside exactly one tile takes that tile's value unchanged (a one-tile grid
+ * reproduces dac_sde_reverse bit for bit); otherwise (sum_k w_k eps_k) / (sum_k w_k) over the
+ * covering tiles in ascending k, w = wy * wx with the per-axis weight min(i + 1, l - i,
+ * overlap + 1) at position i of a tile side l; fp32, multiply and add rounded separately, one
+ * division, no atomics. The result does not depend on tiles_per_forward.
+ * DAC_E_ARG before any device work: a null or empty offset list; th or tw < 2 or larger than
+ * the image; overlap < 0 or >= min(th, tw); an offset out of bounds or not ascending; an axis
+ * the tiles do not cover; tiles_per_forward < 1. DAC_E_STATE while profiling is enabled.
+ * The loop is captured as one hipGraph per (shape, grid contents, tiles per forward, T, mode,
+ * which contexts / noise are given); a loop of more than 65536 graph nodes is enqueued eagerly
+ * on the handle's stream instead, with the same launches and so the same result. */
+int dac_sde_reverse_tiled(dac_handle* h, int mode, float* x_inout, const float* mu,
+                          const float* text_ctx, const float* image_ctx, int B, int H, int W,
+                          int th, int tw, int overlap, const int32_t* ys, int ny,
+                          const int32_t* xs, int nx, int tiles_per_forward, int T,
+                          const float* noise, uint64_t seed, void* stream);
+
+/* Op-level test hook: the blend of dac_sde_reverse_tiled on its own, handle-less (the caller
+ * owns the memory; everything on the current device). eps_tiles [B*ny*nx,3,th,tw] ->
+ * eps_full [B,3,H,W], fp32; ys / xs are host arrays. DAC_E_ARG for the grids
+ * dac_sde_reverse_tiled refuses. Synchronises the stream before it returns. */
+int dac_op_tile_blend(const float* eps_tiles, float* eps_full, int B, int H, int W, int th, int tw,
+                      int overlap, const int32_t* ys, int ny, const int32_t* xs, int nx,
+                      void* stream);
+
 /* Device-noise keying for sharded runs: with noise == NULL, element e of image b draws
  * Philox(seed, step, (first_image + b) * 3*H*W + e), so a shard whose first global image is
  * `first_image` reproduces exactly the noise that image receives in an unsharded batch

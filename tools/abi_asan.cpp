@@ -65,6 +65,26 @@ int main() {
   EXPECT(dac_image_metrics(dummy, dummy, 1, 3, 16, 16, 3, bytes, bytes, rec, rec, nullptr) == DAC_E_ARG);   // cropped 10
   EXPECT(dac_image_metrics(dummy, dummy, 1, 3, 16, 16, -1, bytes, bytes, rec, rec, nullptr) == DAC_E_ARG);
   EXPECT(dac_image_metrics_workspace(1, 3, 11, 11, 0) > 0 && dac_image_metrics_workspace(1, 3, 10, 11, 0) == 0);
+  // Tiled loop: a null handle, and the grid checks (shared with dac_sde_reverse_tiled) through the
+  // handle-less blend hook; every refusal comes before any device work.
+  const int32_t ys2[2] = {0, 16}, xs2[2] = {0, 8}, oob[2] = {0, 20}, desc[2] = {16, 0}, rep[2] = {0, 0},
+                gap[2] = {0, 40}, late[2] = {8, 16}, brief[2] = {0, 4};
+  EXPECT(dac_sde_reverse_tiled(nullptr, 0, dummy, dummy, nullptr, nullptr, 1, 48, 40, 32, 32, 16, ys2, 2, xs2, 2,
+                               16, 1, nullptr, 0, nullptr) == DAC_E_ARG);
+  EXPECT(dac_op_tile_blend(nullptr, nullptr, 1, 48, 40, 32, 32, 16, ys2, 2, xs2, 2, nullptr) == DAC_E_ARG);
+  EXPECT(dac_op_tile_blend(dummy, dummy, 1, 48, 40, 32, 32, 16, nullptr, 2, xs2, 2, nullptr) == DAC_E_ARG);
+  EXPECT(dac_op_tile_blend(dummy, dummy, 1, 48, 40, 32, 32, 16, ys2, 2, xs2, 0, nullptr) == DAC_E_ARG);
+  EXPECT(dac_op_tile_blend(dummy, dummy, 0, 48, 40, 32, 32, 16, ys2, 2, xs2, 2, nullptr) == DAC_E_ARG);     // B
+  EXPECT(dac_op_tile_blend(dummy, dummy, 1, 48, 40, 1, 32, 0, ys2, 1, xs2, 2, nullptr) == DAC_E_ARG);       // th < 2
+  EXPECT(dac_op_tile_blend(dummy, dummy, 1, 48, 40, 32, 48, 16, ys2, 2, xs2, 1, nullptr) == DAC_E_ARG);     // tw > W
+  EXPECT(dac_op_tile_blend(dummy, dummy, 1, 48, 40, 32, 32, -1, ys2, 2, xs2, 2, nullptr) == DAC_E_ARG);
+  EXPECT(dac_op_tile_blend(dummy, dummy, 1, 48, 40, 32, 32, 32, ys2, 2, xs2, 2, nullptr) == DAC_E_ARG);     // overlap
+  EXPECT(dac_op_tile_blend(dummy, dummy, 1, 48, 40, 32, 32, 16, oob, 2, xs2, 2, nullptr) == DAC_E_ARG);
+  EXPECT(dac_op_tile_blend(dummy, dummy, 1, 48, 40, 32, 32, 16, desc, 2, xs2, 2, nullptr) == DAC_E_ARG);
+  EXPECT(dac_op_tile_blend(dummy, dummy, 1, 48, 40, 32, 32, 16, ys2, 2, rep, 2, nullptr) == DAC_E_ARG);
+  EXPECT(dac_op_tile_blend(dummy, dummy, 1, 48, 40, 8, 32, 4, gap, 2, xs2, 2, nullptr) == DAC_E_ARG);       // rows 8..39
+  EXPECT(dac_op_tile_blend(dummy, dummy, 1, 48, 40, 32, 32, 16, late, 2, xs2, 2, nullptr) == DAC_E_ARG);    // row 0
+  EXPECT(dac_op_tile_blend(dummy, dummy, 1, 48, 40, 32, 32, 16, ys2, 2, brief, 2, nullptr) == DAC_E_ARG);   // last columns
   std::printf("build: %s\n", dac_build_id());
 
   // Unsupported UNet configurations fail in dac_create, and the half-built handle is freed.
