@@ -336,6 +336,72 @@ int dac_op_attention(const void* qkv, void* out, int B, int L, int H, int dtype,
   return hipGetLastError() == hipSuccess ? DAC_OK : DAC_E_HIP;
 }
 
+namespace {
+
+// Argument checks shared by the two LinearAttention hooks: everything the launchers would throw
+// on (or index out of bounds with) is refused here, before the first device call.
+bool la_op_args_ok(int B, int HW, int C, int dtype) {
+  if (B < 1 || HW < 1 || (C != 64 && C != 128 && C != 256)) return false;
+  if (dtype != DAC_F32 && dtype != DAC_BF16 && dtype != DAC_F16) return false;
+  return !(dtype == DAC_F32 && C == 256);
+}
+
+// Scratch of an op hook: freed on every path.
+struct DevBuf {
+  void* p = nullptr;
+  bool alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1) == hipSuccess; }
+  ~DevBuf() { if (p) (void)hipFree(p); }
+};
+
+}  // namespace
+
+int dac_op_linear_attention(const void* x, const void* wqkv, const float* wout, const float* bout,
+                            const float* gout, void* y, int B, int HW, int C, int dtype,
+                            float qshift, void* stream) {
+  if (!x || !wqkv || !wout || !bout || !gout || !y || !la_op_args_ok(B, HW, C, dtype) ||
+      !(qshift >= 0.f))
+    return DAC_E_ARG;
+  const hipStream_t st = (hipStream_t)stream;
+  const size_t es = dtype == DAC_F32 ? 4 : 2;
+  DevBuf weff, ws;
+  if (!weff.alloc((size_t)B * C * 128 * es) ||
+      !ws.alloc(dac::linear_attention_fused_ws_floats(B, HW) * sizeof(float)))
+    return DAC_E_NOMEM;
+  hipError_t e = hipSuccess;
+  try {
+    if (dtype == DAC_BF16)
+      dac::linear_attention_fused<__bf16>(x, wqkv, wout, bout, gout, weff.p, y, B, HW, C, (float*)ws.p, st, qshift);
+    else if (dtype == DAC_F16)
+      dac::linear_attention_fused<_Float16>(x, wqkv, wout, bout, gout, weff.p, y, B, HW, C, (float*)ws.p, st, qshift);
+    else
+      dac::linear_attention_fused<float>(x, wqkv, wout, bout, gout, weff.p, y, B, HW, C, (float*)ws.p, st, qshift);
+    e = hipGetLastError();
+  } catch (const std::exception&) {
+    (void)hipStreamSynchronize(st);
+    return DAC_E_ARG;
+  }
+  const hipError_t es2 = hipStreamSynchronize(st);
+  return e == hipSuccess && es2 == hipSuccess ? DAC_OK : DAC_E_HIP;
+}
+
+int dac_op_linear_attention_weff(const void* qkv, const float* wout, void* weff, int B, int HW, int C,
+                                 int dtype, float hw_scale, void* stream) {
+  if (!qkv || !wout || !weff || !la_op_args_ok(B, HW, C, dtype) || !(hw_scale >= 0.f))
+    return DAC_E_ARG;
+  const hipStream_t st = (hipStream_t)stream;
+  DevBuf ws;
+  if (!ws.alloc(dac::linear_attention_ws_floats(B, HW) * sizeof(float))) return DAC_E_NOMEM;
+  if (dtype == DAC_BF16)
+    dac::linear_attention_weff<__bf16>(qkv, wout, weff, B, HW, C, (float*)ws.p, st, hw_scale);
+  else if (dtype == DAC_F16)
+    dac::linear_attention_weff<_Float16>(qkv, wout, weff, B, HW, C, (float*)ws.p, st, hw_scale);
+  else
+    dac::linear_attention_weff<float>(qkv, wout, weff, B, HW, C, (float*)ws.p, st, hw_scale);
+  const hipError_t e = hipGetLastError();
+  const hipError_t es = hipStreamSynchronize(st);
+  return e == hipSuccess && es == hipSuccess ? DAC_OK : DAC_E_HIP;
+}
+
 size_t dac_image_metrics_workspace(int B, int C, int H, int W, int crop_border) {
   return dac::image_metrics_ws_bytes(B, C, H, W, crop_border);
 }

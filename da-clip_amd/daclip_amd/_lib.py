@@ -39,7 +39,8 @@ EXPORTS = ["dac_create", "dac_destroy", "dac_set_weight", "dac_finalize_weights"
            "dac_set_noise_offset", "dac_posterior_step", "dac_unet_flops", "dac_encode_flops", "dac_profile_enable",
            "dac_profile_read", "dac_profile_mode", "dac_profile_launch", "dac_profile_graph_ms",
            "dac_op_attention", "dac_image_metrics_workspace", "dac_image_metrics", "dac_last_error",
-           "dac_sde_reverse_tiled", "dac_op_tile_blend"]
+           "dac_sde_reverse_tiled", "dac_op_tile_blend", "dac_op_linear_attention",
+           "dac_op_linear_attention_weff"]
 
 
 class DacConfig(ctypes.Structure):
@@ -95,6 +96,8 @@ def lib() -> ctypes.CDLL:
                                    ctypes.c_char_p, I, ctypes.c_char_p, I]),
         "dac_profile_graph_ms": (I, [P, ctypes.POINTER(D)]),
         "dac_op_attention": (I, [P, P, I, I, I, I, I, P]),
+        "dac_op_linear_attention": (I, [P, P, P, P, P, P, I, I, I, I, F, P]),
+        "dac_op_linear_attention_weff": (I, [P, P, P, I, I, I, I, F, P]),
         "dac_image_metrics_workspace": (ctypes.c_size_t, [I, I, I, I, I]),
         "dac_image_metrics": (I, [P, P, I, I, I, I, I, P, P, P, P, P]),
         "dac_last_error": (ctypes.c_char_p, [P]),

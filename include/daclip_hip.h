@@ -235,6 +235,30 @@ enum { DAC_ATTN_Q_PRESCALED = 8 };
 int dac_op_attention(const void* qkv, void* out, int B, int L, int H, int dtype, int variant,
                      void* stream);
 
+/* Op-level test hooks: the LinearAttention kernels on their own, handle-less (the caller owns
+ * x / y / the weights; everything on the current device). Both allocate their scratch, run on
+ * `stream`, synchronise it and free the scratch before they return.
+ *
+ * dac_op_linear_attention: the fused block Residual(PreNorm(LinearAttention)) exactly as the
+ * engine launches it: y = x + LN(to_out(ctx^T softmax_d(q))) * gout. x, y: [B*HW, C] in `dtype`;
+ * wqkv: to_qkv [384][C] in `dtype` (q | k | v rows, the PreNorm gain folded in); wout [C][128],
+ * bout [C], gout [C]: fp32. qshift > 0: a bound on every |q|, used as the q-softmax shift (what
+ * the engine derives from the weights when it is <= 40); 0: the per-pixel max.
+ *
+ * dac_op_linear_attention_weff: the unfused context chain on qkv [B*HW, 384] in `dtype`
+ * (q | k | v): weff [B][C][128] in `dtype`, W_eff[b][c][h*32+d] = sum_e Wout[c][h*32+e]
+ * ctx[b][h][d][e] / HW in the natural layout; hw_scale > 0 replaces the 1/HW (fp16 handles pass
+ * S / HW, S the power of two >= HW).
+ *
+ * DAC_E_ARG, before any device work, for: a null pointer; B or HW < 1; C not in {64, 128, 256};
+ * dtype not DAC_F32 / DAC_BF16 / DAC_F16; DAC_F32 with C = 256 (no fp32 kernel of that width);
+ * a negative (or NaN) qshift / hw_scale. */
+int dac_op_linear_attention(const void* x, const void* wqkv, const float* wout, const float* bout,
+                            const float* gout, void* y, int B, int HW, int C, int dtype,
+                            float qshift, void* stream);
+int dac_op_linear_attention_weff(const void* qkv, const float* wout, void* weff, int B, int HW, int C,
+                                 int dtype, float hw_scale, void* stream);
+
 /* Evaluation metrics of config/daclip-sde/test.py:131-196 on the device, handle-less (the
  * caller owns all memory; everything on the current device). out / gt: fp32 [B,C,H,W] RGB,
  * C in {1, 3}. out_bytes / gt_bytes: uint8 [B,H,W,C], BGR for C = 3, what util.tensor2img

@@ -54,6 +54,20 @@ int main() {
   EXPECT(dac_op_attention(dummy, dummy, 1, 64, 1, 99, 0, nullptr) == DAC_E_ARG);      // bad dtype
   EXPECT(dac_op_attention(dummy, dummy, 1, 100, 1, DAC_F32, 2, nullptr) == DAC_E_ARG); // variant 2: fp32
   EXPECT(dac_op_attention(dummy, dummy, 1, 2048, 1, DAC_BF16, 3, nullptr) == DAC_E_ARG); // L > 1024
+  // LinearAttention op hooks: null pointers, sizes, widths, dtypes, fp32 at C = 256 and negative
+  // shifts / scales are refused before any device work.
+  EXPECT(dac_op_linear_attention(nullptr, dummy, dummy, dummy, dummy, dummy, 1, 64, 64, DAC_BF16, 0.f, nullptr) == DAC_E_ARG);
+  EXPECT(dac_op_linear_attention(dummy, dummy, dummy, dummy, dummy, nullptr, 1, 64, 64, DAC_BF16, 0.f, nullptr) == DAC_E_ARG);
+  EXPECT(dac_op_linear_attention(dummy, dummy, dummy, dummy, dummy, dummy, 0, 64, 64, DAC_BF16, 0.f, nullptr) == DAC_E_ARG);
+  EXPECT(dac_op_linear_attention(dummy, dummy, dummy, dummy, dummy, dummy, 1, 0, 64, DAC_BF16, 0.f, nullptr) == DAC_E_ARG);
+  EXPECT(dac_op_linear_attention(dummy, dummy, dummy, dummy, dummy, dummy, 1, 64, 96, DAC_BF16, 0.f, nullptr) == DAC_E_ARG);
+  EXPECT(dac_op_linear_attention(dummy, dummy, dummy, dummy, dummy, dummy, 1, 64, 256, DAC_F32, 0.f, nullptr) == DAC_E_ARG);
+  EXPECT(dac_op_linear_attention(dummy, dummy, dummy, dummy, dummy, dummy, 1, 64, 64, DAC_FP8, 0.f, nullptr) == DAC_E_ARG);
+  EXPECT(dac_op_linear_attention(dummy, dummy, dummy, dummy, dummy, dummy, 1, 64, 64, DAC_F16, -1.f, nullptr) == DAC_E_ARG);
+  EXPECT(dac_op_linear_attention_weff(nullptr, dummy, dummy, 1, 64, 64, DAC_BF16, 0.f, nullptr) == DAC_E_ARG);
+  EXPECT(dac_op_linear_attention_weff(dummy, dummy, dummy, 1, 64, 32, DAC_BF16, 0.f, nullptr) == DAC_E_ARG);
+  EXPECT(dac_op_linear_attention_weff(dummy, dummy, dummy, 1, 64, 256, DAC_F32, 0.f, nullptr) == DAC_E_ARG);
+  EXPECT(dac_op_linear_attention_weff(dummy, dummy, dummy, 1, 64, 64, DAC_F16, -0.5f, nullptr) == DAC_E_ARG);
   // dac_image_metrics: null pointers and unsupported shapes are refused before any device work.
   unsigned char bytes[4] = {0, 0, 0, 0};
   double rec[8];
