@@ -230,7 +230,7 @@ conv3q_kernel(ConvArgs a, const uint8_t* __restrict__ q8w, const uint8_t* __rest
 
 bool conv3q_ok(const ConvArgs& a) {
   return a.xs8 && !a.x2 && a.Cin == 64 && a.C1 >= 64 && a.Cout == 64 && a.K == 576 && a.ld1 == 64 && !a.up &&
-         a.Ho == a.Hs && a.Wo == a.Ws && a.Wo % C3Q_SEG == 0 && a.zero && a.amode == 0 && a.w_bstride == 0 &&
+         a.Ho == a.Hs && a.Wo == a.Ws && a.Wo % C3Q_SEG == 0 && a.amode == 0 && a.w_bstride == 0 &&
          !a.ln_g && !a.lnf_cs && !a.gna_stats && !a.y2 && !a.ys8 && a.cwrap == 0 &&
          (a.act == ACT_NONE || a.act == ACT_SILU) && a.ldy % 8 == 0 && (!a.res1 || a.ldr1 % 8 == 0) && !a.res2 &&
          !a.bbias && !(a.ss && a.res1) && (!a.ss || (a.ss_ld % 4 == 0 && ((uintptr_t)a.ss & 15) == 0)) &&
@@ -239,9 +239,9 @@ bool conv3q_ok(const ConvArgs& a) {
 
 template <typename T>
 void conv3q(const ConvArgs& a, const uint8_t* q8w, const uint8_t* q8s, hipStream_t st) {
-  if (!conv3q_ok(a) || !q8w || !q8s) throw std::invalid_argument("conv3q: arguments rejected by conv3q_ok");
+  if (!conv3q_ok(a) || !a.zero || !q8w || !q8s) throw std::invalid_argument("conv3q: arguments rejected by conv3q_ok");
   const int ntiles = a.B * a.Ho * (a.Wo / C3Q_SEG);
-  conv3q_kernel<T><<<conv3w_blocks(ntiles, C3Q_WAVES), 64 * C3Q_WAVES, 0, st>>>(a, q8w, q8s, ntiles, 6);
+  conv3q_kernel<T><<<conv3w_blocks(ntiles, C3Q_WAVES, conv_launch_knobs().ncu), 64 * C3Q_WAVES, 0, st>>>(a, q8w, q8s, ntiles, 6);
 }
 template void conv3q<bf16>(const ConvArgs&, const uint8_t*, const uint8_t*, hipStream_t);
 template void conv3q<f16>(const ConvArgs&, const uint8_t*, const uint8_t*, hipStream_t);

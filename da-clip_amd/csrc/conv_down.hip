@@ -29,7 +29,7 @@ bool conv_down_ok(const ConvArgs& a) {
   const bool wo_ok = a.Wo >= 32 && (a.Wo % CD_PIX == 0 || (CD_PIX % a.Wo == 0 && (a.Wo & (a.Wo - 1)) == 0));
   const bool epi = (a.act == ACT_NONE || a.act == ACT_SILU) && a.ldy % 8 == 0 && (!a.res1 || a.ldr1 % 8 == 0) &&
                    (!a.res2 || a.ldr2 % 8 == 0) && (!a.ss || (a.ss_ld % 4 == 0 && ((uintptr_t)a.ss & 15) == 0));
-  return a.zero && !a.up && a.amode == 0 && a.w_bstride == 0 && a.cwrap == 0 && !a.ln_g && !a.y2 &&
+  return !a.up && a.amode == 0 && a.w_bstride == 0 && a.cwrap == 0 && !a.ln_g && !a.y2 &&
          a.Cin % 32 == 0 && a.Cout % 64 == 0 && a.K == 16 * a.Cin && a.C1 >= a.Cin && !a.x2 &&
          a.ld1 % 8 == 0 && a.Ho * 2 == a.Hs && a.Wo * 2 == a.Ws && wo_ok &&
          (a.Ho * a.Wo) % CD_PIX == 0 && epi;

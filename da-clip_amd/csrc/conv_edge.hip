@@ -42,7 +42,7 @@ constexpr int C7_BUF = C7_INSTR * 1024;           // bytes per halo buffer
 
 bool conv7_ok(const ConvArgs& a) {
   const int np = a.cwrap ? 2 : 1;
-  return a.Cin == 8 && a.ld1 == 8 && a.Cout == 64 && a.K == np * 7 * 8 * 8 && !a.x2 && !a.up && a.zero &&
+  return a.Cin == 8 && a.ld1 == 8 && a.Cout == 64 && a.K == np * 7 * 8 * 8 && !a.x2 && !a.up &&
          a.amode == 0 && a.w_bstride == 0 && !a.ss && a.act == ACT_NONE && !a.res1 && !a.res2 && !a.bbias &&
          !a.ln_g && a.ldy % 4 == 0 && a.Ho == a.Hs && a.Wo == a.Ws;
 }
@@ -199,7 +199,7 @@ bool conv3n_ok(const ConvArgs& a) {
   const bool dual = a.Cin == 128 && a.x2 == a.x1 && a.ld2 == a.ld1 && a.C1 == 64 && a.cwrap == 0;
   const bool plain = a.Cin == 64 && a.C1 >= 64 && !a.x2;
   return (dual || plain) && a.K == 9 * a.Cin && a.Cout >= 1 && a.Cout <= 4 && a.ld1 % 8 == 0 && !a.up &&
-         a.zero && a.amode == 0 && a.w_bstride == 0 && !a.ss && a.act == ACT_NONE && !a.res1 && !a.res2 &&
+         a.amode == 0 && a.w_bstride == 0 && !a.ss && a.act == ACT_NONE && !a.res1 && !a.res2 &&
          !a.bbias && !a.ln_g && a.Ho == a.Hs && a.Wo == a.Ws && a.Wo % CN_SEG == 0 && a.Ho % CN_R == 0 &&
          a.ldy >= a.Cout;
 }

@@ -14,6 +14,7 @@
 #pragma once
 #include "common.h"
 #include "kernels.h"
+#include "conv_plan.h"   // the EPI_* epilogue kinds
 
 namespace dac {
 
@@ -56,16 +57,6 @@ constexpr int epi_rows(int budget) {
     if (BM % r == 0 && EpiLds<1, BN>::LDW * 4 * r <= budget) best = r;
   return best;
 }
-
-// Epilogue feature set compiled into a kernel (EPK bits). A kernel that can only meet the
-// fast case (tile inside one image, SiLU / none, 16-byte aligned rows) compiles EPI_MIN and
-// stays small: the epilogue runs once per block, and every path compiled into it costs
-// instruction-cache fetches on that one pass.
-enum : int { EPI_GENERAL = 1, EPI_GEGLU = 2, EPI_GELU = 4, EPI_SCALAR = 8, EPI_MIN = 0, EPI_ALL = 15,
-             EPI_LN = 16, EPI_SWAP = 32,   // EPI_SWAP: swapped operands + epi_regs16 (conv_impl.h)
-             EPI_LNF = 64,                 // input LayerNorm folded into a 1x1 GEMM (ConvArgs::lnf_cs)
-             EPI_GNA = 128,                // input GroupNorm applied in the A path (ConvArgs::gna_stats)
-             EPI_PART = 256 };             // split-K partial sums to ConvArgs::part (no epilogue)
 
 // Per-channel epilogue terms of this lane's accumulator columns (bias, 1 + scale, shift) for a
 // tile inside image bimg; kernels that know bimg up front load them before the main loop.

@@ -15,9 +15,12 @@
 #pragma once
 #include <cstdio>
 #include <cstdlib>
+#include <stdexcept>
+#include <string>
 #include <type_traits>
 #include "common.h"
 #include "kernels.h"
+#include "conv_plan.h"
 #include "conv_epi.h"
 
 namespace dac {
@@ -901,20 +904,6 @@ __global__ void __launch_bounds__(64 * WGM * WGN) conv2_kernel(ConvArgs a) {
 // RW + 2 columns once, and the three kw taps read shifted windows of it, so every input
 // pixel of a row band is fetched once per kh instead of once per tap (im2col x3 -> x1).
 // The stage also holds the 3 (kw) weight tiles. Two LDS stages, LDS-DMA fill.
-// Row width of a v3 tile of BM pixels for this output, or 0 if the shape does not tile.
-inline int conv3_rw(const ConvArgs& a, int BM = 256) {
-  const int Wo = a.Wo, Ho = a.Ho;
-  if (Wo <= 0 || (Wo & (Wo - 1))) {
-    if (Wo % BM == 0) return BM;
-    return 0;
-  }
-  const int RW = Wo < BM ? Wo : BM;
-  if (RW < 16) return 0;
-  const int RH = BM / RW;
-  if (Ho % RH) return 0;
-  return RW;
-}
-
 // CK = bytes of one LDS row (one K chunk of one pixel): 128 (8 slots) or 64 (4 slots). A
 // wave-instruction of global_load_lds fills 64 / SLOTS rows; slot swizzle sl ^ f(row). An A
 // fragment's 16 rows start at any row (the kw tap shifts them by 0..2 and output rows start at
@@ -1613,119 +1602,6 @@ conv3i_kernel(ConvArgs a, int RW) {
   }
 }
 
-// Conv3 kernel choice override for microbenchmarks (tools/convbench): -1 = built-in choice,
-// 0 = v3 only, k > 0 = v4 configuration k of conv3i_launch.
-extern int g_conv3_force;
-extern int g_conv2_force;     // 1x1 v2 configuration override (convbench), 0 = built-in
-extern int g_conv2_force32;   // the same, small images only (DAC_CONV2_FORCE32)
-extern int g_conv3_buf;       // v4 buffer-resource DMA (FL bit 10); DAC_CONV3_BUF=0 disables
-extern int g_conv3h_on;       // v6 2-D halo kernel: 0 off, 1 measured-faster shapes, 2 all (DAC_CONV3H)
-// Ring depth of the plain v4 swapped tiles (no fused res_conv, no phase form) when the grid is at
-// most one block per CU (the 64x64 / 32x32 levels at B = 8): with no co-resident block to cover a
-// stage's DMA, deeper rings keep more of it in flight (DAC_C3I_ST = 2 / 3 / 4; 3 measured best: 32x32
-// 256->256 21.6 -> 18.9 us, 64x64 128->128 18.2 -> 17.6 us in the network, +0.45 % images/s). The stage count only
-// buffers: every output is the same ordered sum, so the choice leaves results bit-identical.
-extern int g_c3i_st;
-extern int g_geglu_sw;
-inline int c3i_small_st(const ConvArgs& a, int BM) {
-  const long tiles = (long)a.B * a.Ho * a.Wo / BM * ((a.Cout + 63) / 64);
-  return tiles <= 256 ? g_c3i_st : 2;
-}
-inline bool conv3h_pick(const ConvArgs& a) {
-  return g_conv3h_on == 2 || (g_conv3h_on == 1 && a.Cin >= 128 && !a.res1 && !a.res2 && !a.bbias);
-}
-
-template <typename T, int BM, int BN, int WGM, int WGN, int CK, int ST, int FL = 0, int EPK = EPI_MIN, int WPE = 2>
-bool conv3i_try(const ConvArgs& a, hipStream_t st) {
-  constexpr int WTM = BM / WGM, BKE = CK / sizeof(T);
-  const int RW = conv3_rw(a, BM);
-  if (RW <= 0 || RW % WTM || a.Cin % BKE || (a.C1 < a.Cin && a.C1 % BKE)) return false;
-  if constexpr ((FL & 1024) != 0) {   // buffer-resource DMA: one row pitch, 31-bit byte offsets
-    constexpr size_t LIM = (size_t)1 << 30;
-    if (a.x2 && a.C1 < a.Cin && a.ld2 != a.ld1) return false;
-    if ((size_t)a.B * a.Hs * a.Ws * a.ld1 * sizeof(T) >= LIM || (size_t)a.Cout * a.K * sizeof(T) >= LIM) return false;
-  }
-  if constexpr ((FL & 16) != 0)   // fused res_conv: writes y2 from w2, so both must be given
-    if (!a.y2 || !a.w2) return false;
-  if constexpr ((FL & 8192) != 0) {   // row-phase upsample tiles: one parity per tile
-    if (!a.up || !a.uph || a.Ho % (2 * (BM / RW))) return false;
-    // column-phase too (FL bit 14): uph == 2, K = 16 Cin, rows of >= 128 output pixels
-    if (((FL & 16384) != 0) != (a.uph == 2)) return false;
-    if ((FL & 16384) && RW < 128) return false;
-  } else if (a.uph) {
-    return false;
-  }
-  if constexpr ((FL & 8) != 0)    // swapped tiles DMA the scale / shift / bias rows in 16-byte pieces
-    if ((a.ss && (a.ss_ld % 4 || (a.Cout % 4) || ((uintptr_t)a.ss & 15))) || ((uintptr_t)a.bias & 15)) return false;
-  dim3 g(a.B * a.Ho * a.Wo / BM, (a.Cout + BN - 1) / BN, 1);
-  conv3i_kernel<T, BM, BN, WGM, WGN, CK, ST, FL, EPK, WPE><<<g, 64 * WGM * WGN, 0, st>>>(a, RW);
-  return true;
-}
-template <typename T>
-bool conv3i_launch(int cfg, const ConvArgs& a, hipStream_t st) {
-  switch (cfg) {
-    case 2: return conv3i_try<T, 256, 64, 4, 1, 64, 2>(a, st);
-    case 4: return conv3i_try<T, 128, 128, 2, 2, 64, 2>(a, st);
-    case 11: return conv3i_try<T, 256, 64, 4, 1, 64, 2, 1>(a, st);
-    case 12: return conv3i_try<T, 256, 64, 4, 1, 64, 2, 2>(a, st);
-    case 13: return conv3i_try<T, 256, 64, 4, 1, 64, 2, 3>(a, st);
-    case 14: return conv3i_try<T, 256, 128, 4, 2, 64, 2, 1>(a, st);
-    case 15: return conv3i_try<T, 256, 128, 4, 2, 64, 2, 3>(a, st);
-    case 16: return conv3i_try<T, 256, 64, 4, 1, 64, 3, 1>(a, st);
-    case 17: return conv3i_try<T, 256, 64, 4, 1, 64, 2, 5>(a, st);
-    case 19: return conv3i_try<T, 64, 128, 2, 2, 64, 2, 4>(a, st);
-    case 20: return conv3i_try<T, 128, 64, 4, 1, 64, 2, 4>(a, st);
-    case 22: return conv3i_try<T, 64, 64, 2, 1, 64, 2, 4>(a, st);
-    case 18: return conv3i_try<T, 256, 64, 4, 1, 64, 2, 4>(a, st);
-    case 8: return conv3i_try<T, 128, 128, 4, 2, 64, 3, 3>(a, st);
-    case 9: return conv3i_try<T, 128, 128, 4, 2, 64, 2, 3>(a, st);
-    case 10: return conv3i_try<T, 128, 64, 4, 1, 64, 2, 3>(a, st);
-    case 40:
-      if constexpr (sizeof(T) == 2) return a.Cout % 64 == 0 && conv3i_try<T, 256, 64, 4, 1, 64, 2, 12>(a, st);
-      return false;
-    case 41:
-      if constexpr (sizeof(T) == 2) return a.Cout % 64 == 0 && conv3i_try<T, 128, 64, 4, 1, 64, 2, 12>(a, st);
-      return false;
-    case 48:   // 40 / 41 with buffer-resource DMA
-      if constexpr (sizeof(T) == 2) return a.Cout % 64 == 0 && conv3i_try<T, 256, 64, 4, 1, 64, 2, 12 | 1024>(a, st);
-      return false;
-    case 49:
-      if constexpr (sizeof(T) == 2) return a.Cout % 64 == 0 && conv3i_try<T, 128, 64, 4, 1, 64, 2, 12 | 1024>(a, st);
-      return false;
-    case 52:   // 48 with s_setprio(1) around each stage's MFMAs (FL bit 2)
-      if constexpr (sizeof(T) == 2) return a.Cout % 64 == 0 && conv3i_try<T, 256, 64, 4, 1, 64, 2, 12 | 1024 | 4>(a, st);
-      return false;
-    case 53:   // 48 with sched_barrier fences around each stage (FL bit 0)
-      if constexpr (sizeof(T) == 2) return a.Cout % 64 == 0 && conv3i_try<T, 256, 64, 4, 1, 64, 2, 12 | 1024 | 1>(a, st);
-      return false;
-    case 50:   // diagnostic: 48 with every A row read from a 256-pixel (L2-resident) window
-      if constexpr (sizeof(T) == 2) return a.Cout % 64 == 0 && conv3i_try<T, 256, 64, 4, 1, 64, 2, 12 | 1024 | 2048>(a, st);
-      return false;
-    case 51:   // diagnostic: 50 without the epilogue
-      if constexpr (sizeof(T) == 2) return a.Cout % 64 == 0 && conv3i_try<T, 256, 64, 4, 1, 64, 2, 12 | 1024 | 2048 | 128>(a, st);
-      return false;
-    case 42:   // diagnostics (convbench only; results are garbage): 40 without DMA / without MFMA
-      if constexpr (sizeof(T) == 2) return a.Cout % 64 == 0 && conv3i_try<T, 256, 64, 4, 1, 64, 2, 12 | 32>(a, st);
-      return false;
-    case 43:
-      if constexpr (sizeof(T) == 2) return a.Cout % 64 == 0 && conv3i_try<T, 256, 64, 4, 1, 64, 2, 12 | 64>(a, st);
-      return false;
-    case 44:   // diagnostics: no DMA and no epilogue / no DMA and no barrier / both / no epilogue
-      if constexpr (sizeof(T) == 2) return a.Cout % 64 == 0 && conv3i_try<T, 256, 64, 4, 1, 64, 2, 12 | 32 | 128>(a, st);
-      return false;
-    case 45:
-      if constexpr (sizeof(T) == 2) return a.Cout % 64 == 0 && conv3i_try<T, 256, 64, 4, 1, 64, 2, 12 | 32 | 256>(a, st);
-      return false;
-    case 46:
-      if constexpr (sizeof(T) == 2) return a.Cout % 64 == 0 && conv3i_try<T, 256, 64, 4, 1, 64, 2, 12 | 32 | 128 | 256>(a, st);
-      return false;
-    case 47:
-      if constexpr (sizeof(T) == 2) return a.Cout % 64 == 0 && conv3i_try<T, 256, 64, 4, 1, 64, 2, 12 | 128>(a, st);
-      return false;
-    default: return false;
-  }
-}
-
 // v5: weight-stationary 3x3 conv for Cin = Cout = 64 (16-bit types), the ResBlock convs of the
 // 256x256 / 128x128 levels, whose K = 576 is too short for v4's per-stage weight copies to
 // amortise. The block loads all 9 taps x 64 x 64 weights (72 KB) into LDS once and then
@@ -1944,680 +1820,120 @@ __global__ void __launch_bounds__(64 * NWV) conv3w_kernel(ConvArgs a, int ntiles
 }
 
 // ---------------------------------------------------------------------------------------
-// v6 (3x3, stride 1, pad 1, 16-bit): 2-D halo tiles, one stage per 32-channel chunk.
-// A tile is 8 output rows x 64 columns of one image x 64 output channels; wave w (of 8) owns
-// output row w (64 pixels, TM = 4 interleaved 16-pixel MFMA tiles as in v4) x all 64 channels
-// (swapped operands: weights as the MFMA A operand, so each lane ends with 16 consecutive
-// channels of one pixel and the register epilogue epi_regs16 writes them).
-// One stage holds, for one 32-channel chunk, the whole 10 x 66 input halo of the tile (each
-// input pixel landed in LDS once per chunk, not once per kh as in v4's (chunk, kh) stages)
-// and all 9 weight taps (576 rows): 78 KB, two stages + two epilogue-term slots = 158 KB, one
-// block of 8 waves per CU. Per stage a wave reads 3 x (6 A + 3 x 4 B) fragments and issues 144
-// MFMAs; one barrier per stage (v4: one per 48 MFMAs). LDS-DMA bytes per output are 0.46x v4's
-// (v4's 256 x 64 tiles re-fetch the halo for every kh and the taps for every 256 pixels), which
-// takes the CU's LDS-DMA landing rate off the critical path.
-// Persistent: each block walks tiles of its XCD's contiguous tile range (n-tile fastest, so
-// the blocks of an XCD share halo rows in L2); the next tile's first stage (and its epilogue
-// terms) is DMA'd at the last stage's barrier, under that stage's MFMAs and the epilogue.
-// Buffer-descriptor DMA with out-of-range zero fill for the padding (as v4 FL bit 10).
-constexpr int C3H_RH = 8, C3H_RW = 64, C3H_HWID = C3H_RW + 2;
-constexpr int C3H_NPIX = (C3H_RH + 2) * C3H_HWID;              // 660 halo pixels
-constexpr int C3H_NA = (C3H_NPIX + 15) / 16;                    // 42 A DMA instructions
-constexpr int C3H_NB = 9 * 64 / 16;                             // 36 B DMA instructions
-constexpr int C3H_STAGE = (C3H_NA + C3H_NB) * 1024;             // 79872 B
-constexpr int C3H_SMEM = 2 * C3H_STAGE + 2 * 1024;              // + 2 epilogue-term slots
-static_assert(C3H_SMEM <= 160 * 1024, "v6 LDS");
-inline int conv3h_ntiles(const ConvArgs& a) { return a.B * (a.Ho / C3H_RH) * (a.Wo / C3H_RW) * (a.Cout / 64); }
+// The launcher: conv_plan (conv_plan.h) chooses, conv_dispatch runs the one instantiation the
+// plan names. The X-lists below are the instantiated configurations of each kernel family.
 
-// FL bit 0 (the default): the stage's LDS-DMA is issued in three parts, one after each kh's
-// MFMAs, instead of all at the stage start, where every wave of the block issues at once right
-// after the barrier (3-8 % faster; starting the blocks out of phase was 5-20 % slower).
-template <typename T, int FL = 1>
-__global__ void __launch_bounds__(512) conv3h_kernel(ConvArgs a, int ntiles) {
-  StampGuard stamp_guard(a.stamp);                          // in-graph timing (null: off)
-  constexpr int TM = 4, NF = TM + 2, VE = 8, ES = 2;
-  constexpr unsigned OOB = 0x80000000u;
-  using SA = RowSwz<4, TM>;
-  using SB = RowSwz<4, 1>;
-  static_assert(C3H_NPIX % 4 == 0, "A rows: whole permutation groups");
-  __shared__ __attribute__((aligned(1024))) char smem[C3H_SMEM];
-  char* terms = smem + 2 * C3H_STAGE;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int lr = lane & 15, lg = lane >> 4;
-  const int HWo = a.Ho * a.Wo;
-  const int NT = a.Cout / 64, cols = a.Wo / C3H_RW, tiles_img = (a.Ho / C3H_RH) * cols;
-  const int Hin = a.up ? 2 * a.Hs : a.Hs, Win = a.up ? 2 * a.Ws : a.Ws;
-  const int x_bytes = a.B * a.Hs * a.Ws * a.ld1 * ES, w_bytes = a.Cout * a.K * ES;
-  const int nchunk = a.Cin / 32;
-
-  // This block's tiles: XCD x's contiguous range [x*ntiles/8, (x+1)*ntiles/8), dealt round-robin
-  // to the blocks of that XCD (blocks b and b+8 share one; speed only).
-  const int nb = gridDim.x, xcd = blockIdx.x & 7, jx = blockIdx.x >> 3, cx = (nb - xcd + 7) >> 3;
-  const int t_beg = (int)((long)xcd * ntiles / 8), t_end = (int)((long)(xcd + 1) * ntiles / 8);
-  int t = t_beg + jx;
-  if (t >= t_end) return;
-
-  struct Tile { int b, oh0, ow0, n0; };
-  auto tile_of = [&](int tt) {
-    Tile o;
-    const int sp = tt / NT;
-    o.n0 = (tt - sp * NT) * 64;
-    o.b = sp / tiles_img;
-    const int r = sp - o.b * tiles_img;
-    o.oh0 = (r / cols) * C3H_RH;
-    o.ow0 = (r - (r / cols) * cols) * C3H_RW;
-    return o;
-  };
-  // Per-tile DMA tables of this wave: A instruction q = wave + 8j (< 42) fills physical halo rows
-  // 16q .. 16q+15 (lane / 4), B instruction q = wave + 8j (< 36) weight rows 16q .. (tap = row / 64).
-  int a_off[6], b_off[5];
-  auto tables = [&](const Tile& tl) {
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-      const int q = wave + 8 * j;
-      const int P = q * 16 + (lane >> 2);
-      const int R = SA::logical(P);
-      const int hy = R / C3H_HWID, hx = R - hy * C3H_HWID;
-      const int ih = tl.oh0 + hy - 1, iw = tl.ow0 + hx - 1;
-      const bool ok = q < C3H_NA && R < C3H_NPIX && (unsigned)ih < (unsigned)Hin && (unsigned)iw < (unsigned)Win;
-      const int pix = tl.b * a.Hs * a.Ws + (a.up ? (ih >> 1) : ih) * a.Ws + (a.up ? (iw >> 1) : iw);
-      a_off[j] = ok ? (pix * a.ld1 + SA::slot(R, lane & 3) * VE) * ES : (int)OOB;
-    }
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-      const int q = wave + 8 * j;
-      const int row = q * 16 + (lane >> 2);
-      const int tap = row >> 6, n = tl.n0 + wperm64(row & 63);
-      b_off[j] = q < C3H_NB ? (int)(((size_t)n * a.K + tap * a.Cin + SB::slot(row, lane & 3) * VE) * ES) : (int)OOB;
-    }
-  };
-  // Pieces [p0, p1) of this wave's 11 DMA instructions (6 A, then 5 B) of stage (tl, c).
-  auto issue_part = [&](const Tile& tl, int c, int slot, int p0, int p1) {
-    char* st = smem + slot * C3H_STAGE;
-    const int ci0 = c * 32;
-    const bool from1 = ci0 < a.C1;
-    const void* xb = from1 ? a.x1 : a.x2;
-    const int soa = (from1 ? ci0 : ci0 - a.C1) * ES;
-#pragma unroll
-    for (int j = 0; j < 6; ++j)
-      if (j >= p0 && j < p1 && wave + 8 * j < C3H_NA) buf_lds16(xb, x_bytes, st + (wave + 8 * j) * 1024, a_off[j], soa);
-#pragma unroll
-    for (int j = 0; j < 5; ++j)
-      if (6 + j >= p0 && 6 + j < p1 && wave + 8 * j < C3H_NB)
-        buf_lds16(a.w, w_bytes, st + (C3H_NA + wave + 8 * j) * 1024, b_off[j], ci0 * ES);
-  };
-  auto issue = [&](const Tile& tl, int c, int slot, bool with_terms, int tslot) {
-    issue_part(tl, c, slot, 0, 11);
-    if (with_terms && wave == 0) {                 // lanes 0-15 scale, 16-31 shift, 32-47 bias
-      const int part = lane >> 4, l16 = lane & 15;
-      const float* src = reinterpret_cast<const float*>(a.zero);
-      if (part == 0 && a.ss) src = a.ss + (size_t)tl.b * a.ss_ld + tl.n0 + 4 * l16;
-      else if (part == 1 && a.ss) src = a.ss + (size_t)tl.b * a.ss_ld + a.Cout + tl.n0 + 4 * l16;
-      else if (part == 2 && a.bias) src = a.bias + tl.n0 + 4 * l16;
-      __builtin_amdgcn_global_load_lds((gbl_void_t*)src, (lds_void_t*)(terms + tslot * 1024), 16, 0, 0);
-    }
-  };
-
-  // Fragment offsets (stage-relative): A for (kh, s): halo row (wave + kh) * 66 + TM*lr + s.
-  int aoff[3][NF];
-#pragma unroll
-  for (int kh = 0; kh < 3; ++kh)
-#pragma unroll
-    for (int s2 = 0; s2 < NF; ++s2) {
-      const int R = (wave + kh) * C3H_HWID + TM * lr + s2;
-      aoff[kh][s2] = SA::phys(R) * 64 + (SA::slot(R, lg) << 4);
-    }
-  int boff[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int row = 16 * j + lr;
-    boff[j] = C3H_NA * 1024 + row * 64 + (SB::slot(row, lg) << 4);   // + tap * 4096
-  }
-
-  // (Residual-row prefetch into registers, as v4 / v5 do, does not fit the register budget.)
-  constexpr bool pre_ok = false;
-  Tile cur = tile_of(t);
-  tables(cur);
-  issue(cur, 0, 0, true, 0);
-  int g = 0, k = 0;
-  while (true) {
-    const int tn = t + cx;
-    const bool has_next = tn < t_end;
-    const Tile nxt = has_next ? tile_of(tn) : cur;
-    f32x4 acc[TM][4];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    EpiPref<TM> pref;
-    const size_t rowbase = (size_t)cur.b * HWo + (size_t)(cur.oh0 + wave) * a.Wo + cur.ow0;
-    auto pixf = [&](int i) { return rowbase + TM * lr + i; };
-    for (int c = 0; c < nchunk; ++c, ++g) {
-      // Own DMA of stage g landed. At a tile's first stage (after the first tile) the previous
-      // epilogue's 2*TM stores are younger than it and may stay in flight.
-      if (c == 0 && k > 0) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" :: "n"(2 * TM) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-      // Next stage: (cur, c + 1), or the next tile's first chunk (with its terms) at the last.
-      const bool nx = c + 1 < nchunk || has_next;
-      const Tile& tn2 = c + 1 < nchunk ? cur : nxt;
-      const int cn = c + 1 < nchunk ? c + 1 : 0;
-      if (c + 1 == nchunk && has_next) tables(nxt);
-      if constexpr ((FL & 1) == 0) {
-        if (nx) issue(tn2, cn, (g + 1) & 1, c + 1 == nchunk, (k + 1) & 1);
-      } else if (nx && c + 1 == nchunk && wave == 0) {   // terms now; the DMA pieces follow the MFMAs
-        const int part = lane >> 4, l16 = lane & 15;
-        const float* src = reinterpret_cast<const float*>(a.zero);
-        if (part == 0 && a.ss) src = a.ss + (size_t)tn2.b * a.ss_ld + tn2.n0 + 4 * l16;
-        else if (part == 1 && a.ss) src = a.ss + (size_t)tn2.b * a.ss_ld + a.Cout + tn2.n0 + 4 * l16;
-        else if (part == 2 && a.bias) src = a.bias + tn2.n0 + 4 * l16;
-        __builtin_amdgcn_global_load_lds((gbl_void_t*)src, (lds_void_t*)(terms + ((k + 1) & 1) * 1024), 16, 0, 0);
-      }
-      if (c + 1 == nchunk && pre_ok) epi_prefetch<T, TM>(a, cur.n0 + 16 * lg, cur.b, pixf, pref);
-      const char* st = smem + (g & 1) * C3H_STAGE;
-#pragma unroll
-      for (int kh = 0; kh < 3; ++kh) {
-        u32x4 fa[NF];
-#pragma unroll
-        for (int s2 = 0; s2 < NF; ++s2) fa[s2] = *reinterpret_cast<const u32x4*>(st + aoff[kh][s2]);
-#pragma unroll
-        for (int kw = 0; kw < 3; ++kw) {
-          const char* sb = st + (kh * 3 + kw) * 4096;
-          u32x4 fb[4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) fb[j] = *reinterpret_cast<const u32x4*>(sb + boff[j]);
-#pragma unroll
-          for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) Mma<T>::run(acc[i][j], fb[j], fa[i + kw]);
-        }
-        if constexpr ((FL & 1) != 0)
-          if (nx) issue_part(tn2, cn, (g + 1) & 1, 4 * kh, kh == 2 ? 11 : 4 * kh + 4);
-      }
-    }
-    // Epilogue of this tile (terms slot k & 1 landed with its first stage).
-    if (pre_ok) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const int nbch = cur.n0 + 16 * lg;
-    const float* el = reinterpret_cast<const float*>(terms + (k & 1) * 1024) + 16 * lg;
-    float bi[16];
-#pragma unroll
-    for (int e = 0; e < 16; ++e) bi[e] = el[128 + e];
-    if (pre_ok) epi_regs16<T, TM, false, true>(a, acc, bi, nbch, cur.b, pixf, &pref, el);
-    else epi_regs16<T, TM>(a, acc, bi, nbch, cur.b, pixf, nullptr, el);
-    if (!has_next) break;
-    t = tn;
-    cur = nxt;
-    ++k;
-  }
-}
-
-template <typename T>
-void conv3h_launch(const ConvArgs& a, hipStream_t st, int fl = 0) {
-  const int nt = conv3h_ntiles(a);
-  const int grid = nt < 256 ? nt : 256;
-  if (fl == 0) conv3h_kernel<T, 0><<<grid, 512, 0, st>>>(a, nt);
-  else conv3h_kernel<T, 1><<<grid, 512, 0, st>>>(a, nt);
-}
-
-// Kernel shape of the 64 -> 64 3x3 convs: DAC_C3W=<waves>,<TM>,<stages> (tuning), default
-// 8 waves x 64-pixel segments x 2 stages.
-struct C3WCfg { int nwv = 8, tm = 4, nst = 2; };
-// Small grids (fewer 64-pixel segments than two per wave of a full-chip launch: the 128x128
-// level) may take another shape (DAC_C3W_SMALL); DAC_C3W forces one shape everywhere.
-constexpr C3WCfg kC3WSmall{8, 4, 2};
-inline C3WCfg c3w_cfg(bool small = false) {
-  static C3WCfg c = [] {
-    C3WCfg r;
-    if (const char* e = getenv("DAC_C3W")) sscanf(e, "%d,%d,%d", &r.nwv, &r.tm, &r.nst);
-    return r;
-  }();
-  static C3WCfg cs = [] {
-    C3WCfg r = kC3WSmall;
-    if (const char* e = getenv("DAC_C3W")) sscanf(e, "%d,%d,%d", &r.nwv, &r.tm, &r.nst);
-    else if (const char* e2 = getenv("DAC_C3W_SMALL")) sscanf(e2, "%d,%d,%d", &r.nwv, &r.tm, &r.nst);
-    return r;
-  }();
-  return small ? cs : c;
-}
-inline int conv3w_blocks(int ntiles, int nwv) {
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu < 8)
-      ncu = 256;
-  }
-  int nb = (ntiles + nwv - 1) / nwv;
-  if (nb > ncu) nb = ncu;
-  return (nb + 7) / 8 * 8;                          // whole XCD bands
-}
-template <typename T>
-void conv3w_launch(const ConvArgs& a, int delay, hipStream_t st) {
-  const C3WCfg c = c3w_cfg(a.Wo % 64 == 0 && (long)a.B * a.Ho * (a.Wo / 64) < 2L * 256 * C3W_WAVES);
-#define DAC_C3W(NW_, TM_, NS_)                                                                 \
-  if (!a.ys8 && c.nwv == NW_ && c.tm == TM_ && c.nst == NS_ && a.Wo % (16 * TM_) == 0) {       \
-    const int ntiles = a.B * a.Ho * (a.Wo / (16 * TM_));                                        \
-    conv3w_kernel<T, NW_, TM_, NS_><<<conv3w_blocks(ntiles, NW_), 64 * NW_, 0, st>>>(a, ntiles, delay); \
-    return;                                                                                     \
-  }
-  DAC_C3W(8, 2, 3)
-  DAC_C3W(8, 2, 2)
-  DAC_C3W(4, 4, 4)
-  DAC_C3W(4, 4, 3)
-  DAC_C3W(6, 4, 2)
-#undef DAC_C3W
-  const int ntiles = a.B * a.Ho * (a.Wo >> 6);
-  // Buffer-descriptor DMA when the input has one row pitch and 31-bit byte offsets.
-  static const int buf_env = getenv("DAC_C3W_BUF") ? atoi(getenv("DAC_C3W_BUF")) : 1;
-  const bool buf = buf_env && (a.C1 >= a.Cin || !a.x2 || a.ld2 == a.ld1) &&
-                   (size_t)a.B * a.Hs * a.Ws * a.ld1 * 2 + a.ld1 * 2 < ((size_t)1 << 31);
-  if (a.ys8) {                                      // fp8 output (conv_q8out_ok): buffer DMA form only
-    if (!buf) throw std::logic_error("conv3w: fp8 output needs the buffer-descriptor DMA form");
-    conv3w_kernel<T, C3W_WAVES, 4, 2, true, true><<<conv3w_blocks(ntiles, C3W_WAVES), 64 * C3W_WAVES, 0, st>>>(a, ntiles, delay);
-  } else if (buf)
-    conv3w_kernel<T, C3W_WAVES, 4, 2, true><<<conv3w_blocks(ntiles, C3W_WAVES), 64 * C3W_WAVES, 0, st>>>(a, ntiles, delay);
-  else
-    conv3w_kernel<T, C3W_WAVES, 4, 2><<<conv3w_blocks(ntiles, C3W_WAVES), 64 * C3W_WAVES, 0, st>>>(a, ntiles, delay);
-}
-
-// v3 launch, buffer-descriptor DMA when the input has one row pitch and 30-bit byte offsets.
-template <typename T, int BM, int BN, int WGM, int WGN, int CK>
-void conv3_launch(const ConvArgs& a, dim3 g, int RW, hipStream_t st) {
-  constexpr size_t LIM = (size_t)1 << 30;
-  const bool buf = g_conv3_buf && (a.C1 >= a.Cin || !a.x2 || a.ld2 == a.ld1) &&
-                   (size_t)a.B * a.Hs * a.Ws * a.ld1 * sizeof(T) < LIM && (size_t)a.Cout * a.K * sizeof(T) < LIM;
-  if (buf) conv3_kernel<T, BM, BN, WGM, WGN, CK, true><<<g, 64 * WGM * WGN, 0, st>>>(a, RW);
-  else conv3_kernel<T, BM, BN, WGM, WGN, CK><<<g, 64 * WGM * WGN, 0, st>>>(a, RW);
-}
+// conv3i: X(BM, BN, WGM, WGN, ST, FL, EPK), CK = 64. Any element type / 16-bit only (swapped tiles).
+#define DAC_C3I_ANY(X)                                                                                          \
+  X(256, 16, 4, 1, 2, 3, EPI_ALL) X(256, 64, 4, 1, 2, 0, EPI_MIN) X(128, 128, 2, 2, 2, 0, EPI_MIN)              \
+  X(256, 64, 4, 1, 2, 1, EPI_MIN) X(256, 64, 4, 1, 2, 2, EPI_MIN) X(256, 64, 4, 1, 2, 3, EPI_MIN)               \
+  X(256, 128, 4, 2, 2, 1, EPI_MIN) X(256, 128, 4, 2, 2, 3, EPI_MIN) X(256, 64, 4, 1, 3, 1, EPI_MIN)             \
+  X(256, 64, 4, 1, 2, 5, EPI_MIN) X(64, 128, 2, 2, 2, 4, EPI_MIN) X(128, 64, 4, 1, 2, 4, EPI_MIN)               \
+  X(64, 64, 2, 1, 2, 4, EPI_MIN) X(256, 64, 4, 1, 2, 4, EPI_MIN) X(128, 128, 4, 2, 3, 3, EPI_MIN)               \
+  X(128, 128, 4, 2, 2, 3, EPI_MIN) X(128, 64, 4, 1, 2, 3, EPI_MIN)
+#define DAC_C3I_16(X)                                                                                           \
+  X(256, 64, 4, 1, 2, 12, EPI_MIN) X(256, 64, 4, 1, 2, 12 | 1024, EPI_MIN) X(256, 64, 4, 1, 3, 12 | 1024, EPI_MIN) \
+  X(256, 64, 4, 1, 4, 12 | 1024, EPI_MIN) X(256, 64, 4, 1, 2, 12 | 16, EPI_MIN)                                 \
+  X(256, 64, 4, 1, 2, 12 | 16 | 1024, EPI_MIN) X(256, 64, 4, 1, 2, 12 | 16 | 4096, EPI_MIN)                     \
+  X(256, 64, 4, 1, 2, 12 | 16 | 1024 | 4096, EPI_MIN) X(256, 64, 4, 1, 2, 12 | 8192, EPI_MIN)                   \
+  X(256, 64, 4, 1, 2, 12 | 1024 | 8192, EPI_MIN) X(256, 64, 4, 1, 2, 12 | 8192 | 16384, EPI_MIN)                \
+  X(256, 64, 4, 1, 2, 12 | 1024 | 8192 | 16384, EPI_MIN) X(128, 64, 4, 1, 2, 12, EPI_MIN)                       \
+  X(128, 64, 4, 1, 2, 12 | 1024, EPI_MIN) X(128, 64, 4, 1, 3, 12 | 1024, EPI_MIN)                               \
+  X(128, 64, 4, 1, 4, 12 | 1024, EPI_MIN) X(128, 64, 4, 1, 2, 12 | 16, EPI_MIN)                                 \
+  X(128, 64, 4, 1, 2, 12 | 16 | 1024, EPI_MIN)
+// conv3: X(BM, BN, WGM, WGN, CK), each in the flat and the buffer-descriptor DMA form.
+#define DAC_C3(X) X(128, 128, 4, 2, 128) X(128, 64, 2, 2, 64) X(256, 64, 4, 2, 128) X(128, 128, 2, 2, 64)
+// conv2: X(BM, BN, WGM, WGN, ST, EPK). MA = both the minimal and the general epilogue.
+#define DAC_C2_MA(X, BM, BN, WGM, WGN, ST) X(BM, BN, WGM, WGN, ST, EPI_MIN) X(BM, BN, WGM, WGN, ST, EPI_ALL)
+#define DAC_C2_GEN(X) DAC_C2_MA(X, 256, 128, 4, 2, 3) DAC_C2_MA(X, 128, 128, 2, 2, 3) DAC_C2_MA(X, 256, 64, 4, 2, 3)
+#define DAC_C2_1X1(X)                                                                                           \
+  DAC_C2_MA(X, 128, 128, 2, 2, 2) DAC_C2_MA(X, 256, 128, 4, 2, 2) DAC_C2_MA(X, 128, 256, 2, 4, 2)               \
+  DAC_C2_MA(X, 128, 64, 2, 2, 2) DAC_C2_MA(X, 64, 128, 2, 2, 2) DAC_C2_MA(X, 64, 64, 2, 2, 3)                   \
+  DAC_C2_MA(X, 128, 64, 2, 2, 3) DAC_C2_MA(X, 64, 128, 2, 2, 3) DAC_C2_MA(X, 64, 128, 2, 2, 4)                  \
+  DAC_C2_MA(X, 128, 64, 2, 2, 1) X(256, 256, 4, 2, 2, EPI_MIN) X(256, 64, 4, 2, 3, EPI_LN)                      \
+  X(128, 128, 2, 2, 2, EPI_LN) X(64, 128, 2, 2, 2, EPI_PART)
+#define DAC_C2_1X1_16(X)                                                                                        \
+  X(64, 128, 2, 2, 2, EPI_SWAP) X(64, 128, 2, 2, 3, EPI_SWAP) X(64, 128, 2, 2, 4, EPI_SWAP)                     \
+  X(64, 128, 2, 2, 6, EPI_SWAP) X(128, 128, 2, 2, 2, EPI_SWAP) X(128, 128, 2, 2, 3, EPI_SWAP)                   \
+  X(128, 128, 2, 2, 4, EPI_SWAP) X(128, 128, 2, 2, 5, EPI_SWAP) X(256, 64, 4, 1, 2, EPI_SWAP | EPI_LN)          \
+  X(64, 128, 2, 2, 2, EPI_SWAP | EPI_GNA) X(64, 128, 2, 2, 2, EPI_SWAP | EPI_LNF)                               \
+  X(256, 256, 4, 4, 2, EPI_SWAP | EPI_GEGLU) X(128, 256, 2, 4, 2, EPI_SWAP | EPI_GEGLU)                         \
+  X(256, 128, 4, 2, 2, EPI_SWAP | EPI_GEGLU) X(128, 128, 2, 2, 2, EPI_SWAP | EPI_GEGLU)                         \
+  X(256, 256, 4, 2, 2, EPI_GEGLU)
 
 template <typename T, int KH, int KW, int S, int P>
 void conv_dispatch(const ConvArgs& a0, hipStream_t st) {
+  const ConvPlan p = conv_plan(a0, KH, KW, S, P, (int)sizeof(T), conv_launch_knobs());
+  if (p.kind == CONV_NONE) throw std::logic_error(std::string("conv: ") + p.why_not);
+  if (!a0.zero && p.kind != CONV_1) throw std::invalid_argument("conv: no zero page (ConvArgs::zero)");
+  if ((p.kind == CONV_3_SPLIT || p.kind == CONV_2_SPLIT) && !a0.part) throw std::invalid_argument("conv: split-K without a partials buffer");
+  ConvArgs a = a0;
   // 1x1 GEMMs: buffer-descriptor DMA when the input has one row pitch and every byte offset
   // fits 31 bits (ConvArgs::dbuf; DAC_CONV3_BUF=0 disables it with the 3x3 forms).
-  ConvArgs a = a0;
-  a.dbuf = 0;
-  if constexpr (KH == 1 && KW == 1 && S == 1 && P == 0) {
-    constexpr size_t LIM = (size_t)1 << 31;
-    const size_t es = sizeof(T);
-    a.dbuf = g_conv3_buf && (!a.x2 || a.C1 >= a.Cin || a.ld2 == a.ld1) && !a.up &&
-             (size_t)a.B * a.Hs * a.Ws * a.ld1 * es < LIM && (!a.x2 || (size_t)a.B * a.Hs * a.Ws * a.ld2 * es < LIM) &&
-             (size_t)a.Cout * a.K * es < LIM;
-  }
-  // A fused second output is only requested after conv_res_fusable(a) said the v4 path takes it;
-  // no path below may return without writing it.
-  if (a.y2 && !(KH == 3 && KW == 3 && S == 1 && P == 1 && sizeof(T) == 2 && conv_res_fusable(a)))
-    throw std::logic_error("conv: fused second output requested on a shape without a fusing kernel");
-  const int M = a.B * a.Ho * a.Wo;
-  const bool batched = a.w_bstride > 0;
-  const int Mg = batched ? a.Ho * a.Wo : M;
-  const int gz = batched ? a.B : 1;
-  constexpr int BKE = 128 / sizeof(T);
-  // Tap shapes whose Cin is always a multiple of the K tile use v2; v1 serves the rest
-  // (init conv Cin=8, patch embed, final conv Cout=3, LinearAttention to_out amode=1).
-  constexpr bool V2 = (KH == 1 || KH == 3 || KH == 4);
-  const bool v2ok = V2 && a.zero != nullptr && a.Cin % BKE == 0 && a.amode == 0 && a.Cout > 16;
-  if constexpr (KH == 3 && KW == 3 && S == 1 && P == 1) {
-    if (a.ksplit > 1 && a.part) {
-      // Split-K (engine conv_call; conv3_split_ok): v3's 8-wave 128 x 128 form over ksplit Cin
-      // ranges (grid z), then the in-order reduce + epilogue pass.
-      if (!conv3_split_ok(a, (int)sizeof(T))) throw std::invalid_argument("conv: 3x3 split-K on a shape without it");
-      dim3 g(a.B * a.Ho * a.Wo / 128, (a.Cout + 127) / 128, a.ksplit);
-      conv3_launch<T, 128, 128, 4, 2, 128>(a, g, conv3_rw(a, 128), st);
-      conv_part_reduce<T>(a, st);
-      return;
-    }
-  }
-  if constexpr (KH == 3 && KW == 3 && S == 1 && P == 1 && sizeof(T) == 2) {
-    if (g_conv3_force < 0 && conv3n_ok(a)) {   // final_conv: conv_edge.hip
-      conv3n<T>(a, st);
-      return;
+  a.dbuf = KH == 1 && p.buffer_dma;
+  const dim3 g(p.gx, p.gy, p.gz);
+  if constexpr (sizeof(T) == 2) {
+    switch (p.kind) {
+      case CONV_7: if constexpr (KH == 7) conv7<T>(a, st); return;
+      case CONV_3N: if constexpr (KH == 3) conv3n<T>(a, st); return;
+      case CONV_DOWN: if constexpr (KH == 4) conv_down<T>(a, st); return;
+      case CONV_3R: if constexpr (KH == 3) conv3r<T>(a, st); return;
+      case CONV_3W:
+        if constexpr (KH == 3) {
+          const int ntiles = a.B * a.Ho * (a.Wo >> 6);
+          if (p.epi == C3I_Q8) conv3w_kernel<T, C3W_WAVES, 4, 2, true, true><<<g, p.threads, 0, st>>>(a, ntiles, p.delay);
+          else if (p.buffer_dma) conv3w_kernel<T, C3W_WAVES, 4, 2, true><<<g, p.threads, 0, st>>>(a, ntiles, p.delay);
+          else conv3w_kernel<T, C3W_WAVES, 4, 2><<<g, p.threads, 0, st>>>(a, ntiles, p.delay);
+        }
+        return;
+      default: break;
     }
   }
   if constexpr (KH == 3 && KW == 3 && S == 1 && P == 1) {
-    // Narrow output (the final conv, Cout = 3): v4 row-halo tiles with 16 output channels and
-    // the general (scalar-capable) epilogue; the A operand dominates, and v4 reads each input
-    // pixel once per kernel row instead of 9 times.
-    if (a.Cout <= 16 && a.zero && a.amode == 0 && a.w_bstride == 0 && g_conv3_force < 0 &&
-        (a.act == ACT_NONE || a.act == ACT_SILU) && a.Cin % (64 / (int)sizeof(T)) == 0)
-      if (conv3i_try<T, 256, 16, 4, 1, 64, 2, 3, EPI_ALL>(a, st)) return;
-  }
-  if constexpr (KH == 3 && KW == 3 && S == 1 && P == 1 && sizeof(T) == 2) {
-    // v6 (2-D halo tiles): force 60, or DAC_CONV3H=1 for every shape it takes.
-    // v6 (2-D halo tiles): forces 60 / 61 (without / with the interleaved DMA issue); by default
-    // (DAC_CONV3H=1) the plain convs with Cin >= 128 it measured faster on,
-    // DAC_CONV3H=2 every shape it takes, 0 none.
-    if (((g_conv3_force == 60 || g_conv3_force == 61) ||
-         (g_conv3_force < 0 && conv3h_pick(a))) && conv3h_ok(a, (int)sizeof(T))) {
-      conv3h_launch<T>(a, st, g_conv3_force == 60 ? 0 : 1);
-      return;
+    if (p.kind == CONV_3I) {
+      if (!conv3i_fit(a, (int)sizeof(T), p.BM, p.WGM, p.CK, p.fl)) throw std::logic_error("conv: conv3i plan does not fit");
+#define X(BM_, BN_, WGM_, WGN_, ST_, FL_, EPK_)                                                                 \
+      if (p.BM == BM_ && p.BN == BN_ && p.WGM == WGM_ && p.WGN == WGN_ && p.ST == ST_ && p.fl == (FL_) && p.epi == (EPK_)) { \
+        conv3i_kernel<T, BM_, BN_, WGM_, WGN_, 64, ST_, (FL_), (EPK_)><<<g, p.threads, 0, st>>>(a, p.RW);       \
+        return;                                                                                                 \
+      }
+      DAC_C3I_ANY(X)
+      if constexpr (sizeof(T) == 2) { DAC_C3I_16(X) }
+#undef X
     }
-    if ((g_conv3_force < 0 || g_conv3_force == 70) && conv3r_ok(a)) {
-      conv3r<T>(a, st);
-      return;
-    }
-    if ((g_conv3_force < 0 || (g_conv3_force >= 30 && g_conv3_force < 40)) && conv3w_ok(a)) {
-      const int delay = g_conv3_force >= 30 ? (g_conv3_force - 30) * 2 : 6;   // swept: 4-10 best
-      conv3w_launch<T>(a, delay, st);
-      return;
+    if (p.kind == CONV_3 || p.kind == CONV_3_SPLIT) {
+#define X(BM_, BN_, WGM_, WGN_, CK_)                                                                            \
+      if (p.BM == BM_ && p.BN == BN_ && p.WGM == WGM_ && p.CK == CK_) {                                         \
+        if (p.buffer_dma) conv3_kernel<T, BM_, BN_, WGM_, WGN_, CK_, true><<<g, p.threads, 0, st>>>(a, p.RW);   \
+        else conv3_kernel<T, BM_, BN_, WGM_, WGN_, CK_><<<g, p.threads, 0, st>>>(a, p.RW);                      \
+        if (p.kind == CONV_3_SPLIT) conv_part_reduce<T>(a, st);                                                 \
+        return;                                                                                                 \
+      }
+      DAC_C3(X)
+#undef X
     }
   }
-  if constexpr (KH == 4 && KW == 4 && S == 2 && P == 1 && sizeof(T) == 2) {
-    if (g_conv3_force < 0 && conv_down_ok(a)) {
-      conv_down<T>(a, st);
-      return;
+  if (p.kind == CONV_2 || p.kind == CONV_2_SPLIT) {
+    if (p.w_gs) { a.w = a.w_gs; a.bias = a.b_gs; }
+#define X(BM_, BN_, WGM_, WGN_, ST_, EPK_)                                                                      \
+    if (p.BM == BM_ && p.BN == BN_ && p.WGM == WGM_ && p.WGN == WGN_ && p.ST == ST_ && p.epi == (EPK_)) {       \
+      conv2_kernel<T, BM_, BN_, WGM_, WGN_, ST_, KH, KW, S, P, (EPK_)><<<g, p.threads, 0, st>>>(a);             \
+      if (p.kind == CONV_2_SPLIT) conv_part_reduce<T>(a, st);                                                   \
+      return;                                                                                                   \
     }
+    if constexpr (KH == 1 || KH == 3 || KH == 4) { DAC_C2_GEN(X) }
+    if constexpr (KH == 1) { DAC_C2_1X1(X) }
+    if constexpr (KH == 1 && sizeof(T) == 2) { DAC_C2_1X1_16(X) }
+    if constexpr (KH == 7 && sizeof(T) == 2) { X(256, 64, 4, 2, 3, EPI_ALL) }
+#undef X
   }
-  if constexpr (KH == 7 && KW == 7 && S == 1 && P == 3 && sizeof(T) == 2) {
-    if (conv7_ok(a)) {
-      conv7<T>(a, st);
-      return;
-    }
-    if (a.Cin == 8 && a.K == (a.cwrap ? 2 : 1) * 7 * 8 * 8 && a.zero && a.amode == 0 && a.w_bstride == 0 && !a.x2) {
-      const int Mg = a.B * a.Ho * a.Wo;
-      dim3 g((Mg + 255) / 256, (a.Cout + 63) / 64, 1);
-      conv2_kernel<T, 256, 64, 4, 2, 3, KH, KW, S, P, EPI_ALL><<<g, 512, 0, st>>>(a);
-      return;
-    }
-    // cwrap = 1 here means the row-tap dual layout (kernel rows wrap); the generic loaders read
-    // a nonzero cwrap as a channel wrap instead, so no other kernel may take it.
-    if (a.cwrap) throw std::logic_error("conv: 7x7 row-tap dual layout without its kernel");
+  if (p.kind == CONV_1) {
+    if (p.BN == 16) conv_kernel<T, 256, 16, 4, 1, KH, KW, S, P><<<g, 256, 0, st>>>(a);
+    else if (p.BN == 64) conv_kernel<T, 256, 64, 4, 1, KH, KW, S, P><<<g, 256, 0, st>>>(a);
+    else conv_kernel<T, 128, 128, 2, 2, KH, KW, S, P><<<g, 256, 0, st>>>(a);
+    return;
   }
-  if constexpr (KH == 3 && KW == 3 && S == 1 && P == 1) {
-    const int RW = conv3_rw(a);
-    // v3's epilogue is compiled for the fast case only: SiLU / none, 16-byte rows.
-    const bool epi_min = (a.act == ACT_NONE || a.act == ACT_SILU) && a.Cout % (16 / (int)sizeof(T)) == 0 &&
-                         a.ldy % (16 / (int)sizeof(T)) == 0 && (!a.res1 || a.ldr1 % (16 / (int)sizeof(T)) == 0) &&
-                         (!a.res2 || a.ldr2 % (16 / (int)sizeof(T)) == 0);
-    if (v2ok && RW > 0 && a.w_bstride == 0 && epi_min && a.cwrap == 0) {
-      if (g_conv3_force > 0) {
-        if (conv3i_launch<T>(g_conv3_force, a, st)) return;
-      } else if (g_conv3_force < 0) {
-        // v4: 256 x 64 tiles, 4 waves of 64x64, interleaved rows (measured 3-15 % faster than
-        // v3 at every 3x3 shape of the UNet whose row width is a multiple of 64).
-        // bf16 with whole 64-channel tiles: swapped operands + register epilogue (FL bit 3),
-        // 4-9 % faster than the LDS-staged epilogue at every v4 shape of the UNet.
-        if constexpr (sizeof(T) == 2) {
-          // Buffer-resource DMA (FL bit 10) first; the flat-address form takes what it rejects.
-          const int nb = g_conv3_buf ? 1024 : 0;
-          if (a.uph) {                                // row- (and column-) phase upsample conv (conv_uph_ok)
-            if (a.uph == 2 && nb && conv3i_try<T, 256, 64, 4, 1, 64, 2, 12 | 1024 | 8192 | 16384>(a, st)) return;
-            if (a.uph == 2 && conv3i_try<T, 256, 64, 4, 1, 64, 2, 12 | 8192 | 16384>(a, st)) return;
-            if (a.uph == 1 && nb && conv3i_try<T, 256, 64, 4, 1, 64, 2, 12 | 1024 | 8192>(a, st)) return;
-            if (a.uph == 1 && conv3i_try<T, 256, 64, 4, 1, 64, 2, 12 | 8192>(a, st)) return;
-            throw std::logic_error("conv: row-phase upsample conv without a matching v4 tile");
-          }
-          if (a.ys8) {                                // fp8 output (conv_q8out_ok): fused-res tiles only
-            if (a.y2 && a.Cout == 64 && nb && conv3i_try<T, 256, 64, 4, 1, 64, 2, 12 | 16 | 1024 | 4096>(a, st)) return;
-            if (a.y2 && a.Cout == 64 && conv3i_try<T, 256, 64, 4, 1, 64, 2, 12 | 16 | 4096>(a, st)) return;
-            throw std::logic_error("conv: fp8 output without a matching fused v4 tile");
-          }
-          if (a.y2) {
-            if (a.Cout % 64 == 0 && nb && conv3i_try<T, 256, 64, 4, 1, 64, 2, 12 | 16 | 1024>(a, st)) return;
-            if (a.Cout % 64 == 0 && conv3i_try<T, 256, 64, 4, 1, 64, 2, 12 | 16>(a, st)) return;
-            if (a.Cout % 64 == 0 && nb && conv3i_try<T, 128, 64, 4, 1, 64, 2, 12 | 16 | 1024>(a, st)) return;
-            if (a.Cout % 64 == 0 && conv3i_try<T, 128, 64, 4, 1, 64, 2, 12 | 16>(a, st)) return;
-            throw std::logic_error("conv: conv_res_fusable promised a fused kernel");
-          } else if (a.Cout % 64 == 0 && nb && c3i_small_st(a, 256) == 3 && conv3i_try<T, 256, 64, 4, 1, 64, 3, 12 | 1024>(a, st)) {
-            return;
-          } else if (a.Cout % 64 == 0 && nb && c3i_small_st(a, 256) == 4 && conv3i_try<T, 256, 64, 4, 1, 64, 4, 12 | 1024>(a, st)) {
-            return;
-          } else if (a.Cout % 64 == 0 && nb && conv3i_try<T, 256, 64, 4, 1, 64, 2, 12 | 1024>(a, st)) {
-            return;
-          } else if (a.Cout % 64 == 0 && conv3i_try<T, 256, 64, 4, 1, 64, 2, 12>(a, st)) {
-            return;
-          }
-        }
-        if (conv3i_try<T, 256, 64, 4, 1, 64, 2, 4>(a, st)) return;
-        // Rows of 32 (the 32x32 level), Cout <= 256: 128x64 tiles of 32-pixel wave tiles
-        // (TM = 2), 8 % faster than v3 in the UNet; the 512-wide convs stay on v3 (v4 with
-        // 128x128 tiles measured 3-4 % slower there).
-        // (The 512-wide convs stay on v3: v4 128x64 swapped tiles measured 11 % faster in
-        // convbench but 3 % slower in the network.)
-        if constexpr (sizeof(T) == 2)
-          if (a.Cout <= 256 && a.Cout % 64 == 0) {
-            if (g_conv3_buf && c3i_small_st(a, 128) == 3 && conv3i_try<T, 128, 64, 4, 1, 64, 3, 12 | 1024>(a, st)) return;
-            if (g_conv3_buf && c3i_small_st(a, 128) == 4 && conv3i_try<T, 128, 64, 4, 1, 64, 4, 12 | 1024>(a, st)) return;
-            if (g_conv3_buf && conv3i_try<T, 128, 64, 4, 1, 64, 2, 12 | 1024>(a, st)) return;
-            if (conv3i_try<T, 128, 64, 4, 1, 64, 2, 12>(a, st)) return;
-          }
-        if (a.Cout <= 256 && conv3i_try<T, 128, 64, 4, 1, 64, 2, 4>(a, st)) return;
-      }
-      // 64-byte K rows, 4 waves of 64x64 (or 64x32) wave tiles: two 24-36 KB stages, so 2-3
-      // blocks share a CU and one block's LDS-DMA latency hides behind another's MFMAs
-      // (measured 10-24 % faster than one 8-wave block with 128-byte rows). Small grids
-      // (< 2 blocks per CU, the 32x32 level) keep the 8-wave block.
-      if (a.Cout <= 64 && conv3_rw(a, 128) > 0) {
-        dim3 g(a.B * a.Ho * a.Wo / 128, (a.Cout + 63) / 64, 1);
-        conv3_launch<T, 128, 64, 2, 2, 64>(a, g, conv3_rw(a, 128), st);
-        return;
-      }
-      if (a.Cout <= 64) {
-        dim3 g(a.B * a.Ho * a.Wo / 256, (a.Cout + 63) / 64, 1);
-        conv3_launch<T, 256, 64, 4, 2, 128>(a, g, RW, st);
-        return;
-      }
-      if (conv3_rw(a, 128) > 0) {
-        dim3 g(a.B * a.Ho * a.Wo / 128, (a.Cout + 127) / 128, 1);
-        // Chosen from ONE image's tile count (64 = the batch-8 grid's 512): the two forms walk
-        // the channels in different chunk orders (CK), so a batch-size-driven choice made an
-        // image's result depend on its batch (B = 16 vs 1 at the 32x32 level).
-        // The 8-wave form as 4 x 2 waves of 32 x 64 (round 5: +0.3 % in the network against
-        // 2 x 4 waves of 64 x 32, three interleaved pairs; 4 x 4 waves of 32 x 32 no better).
-        if ((long)(a.Ho * a.Wo / 128) * g.y >= 64)
-          conv3_launch<T, 128, 128, 2, 2, 64>(a, g, conv3_rw(a, 128), st);
-        else
-          conv3_launch<T, 128, 128, 4, 2, 128>(a, g, conv3_rw(a, 128), st);
-        return;
-      }
-    }
-  }
-  if constexpr (V2) if (v2ok) {
-    // Minimal epilogue when every tile lies inside one image (tile rows divide H*W, or the
-    // per-image grid) and the tail is SiLU / none on 16-byte rows.
-    constexpr int VEh = 16 / sizeof(T);
-    const bool rows_ok = a.Cout % VEh == 0 && a.ldy % VEh == 0 && (!a.res1 || a.ldr1 % VEh == 0) &&
-                         (!a.res2 || a.ldr2 % VEh == 0);
-    const bool act_ok = a.act == ACT_NONE || a.act == ACT_SILU;
-    const int HWo = a.Ho * a.Wo;
-    auto minimal = [&](int BMv) { return rows_ok && act_ok && (batched || HWo % BMv == 0); };
-#define DAC_V2(BM_, BN_, WGM_, WGN_, ST_, THR_)                                                   \
-    {                                                                                            \
-      dim3 g((Mg + BM_ - 1) / BM_, (a.Cout + BN_ - 1) / BN_, gz);                                \
-      if (minimal(BM_))                                                                          \
-        conv2_kernel<T, BM_, BN_, WGM_, WGN_, ST_, KH, KW, S, P, EPI_MIN><<<g, THR_, 0, st>>>(a); \
-      else                                                                                       \
-        conv2_kernel<T, BM_, BN_, WGM_, WGN_, ST_, KH, KW, S, P, EPI_ALL><<<g, THR_, 0, st>>>(a); \
-      return;                                                                                    \
-    }
-    if constexpr (KH == 1) if (a.ln_g) {
-      // Row-LayerNorm epilogue: one N tile must cover Cout exactly.
-      if constexpr (sizeof(T) == 2)
-        if (minimal(256) && a.Cout == 64 && !a.ss && a.act == ACT_NONE && !a.res2 && !a.bbias) {
-          // One wave owns all 64 channels of its rows: the LN runs in registers.
-          dim3 g((Mg + 255) / 256, 1, gz);
-          conv2_kernel<T, 256, 64, 4, 1, 2, KH, KW, S, P, EPI_SWAP | EPI_LN><<<g, 256, 0, st>>>(a);
-          return;
-        }
-      if (minimal(256) && a.Cout == 64) {
-        dim3 g((Mg + 255) / 256, 1, gz);
-        conv2_kernel<T, 256, 64, 4, 2, 3, KH, KW, S, P, EPI_LN><<<g, 512, 0, st>>>(a);
-        return;
-      }
-      if (minimal(128) && a.Cout == 128) {
-        dim3 g((Mg + 127) / 128, 1, gz);
-        conv2_kernel<T, 128, 128, 2, 2, 2, KH, KW, S, P, EPI_LN><<<g, 256, 0, st>>>(a);
-        return;
-      }
-      throw std::logic_error("conv: shape the engine never requests");
-    }
-    if constexpr (KH == 1) if (a.gna_stats) {
-      // Input GroupNorm in the A path (conv_gna_ok mirrors this choice).
-      if constexpr (sizeof(T) == 2)
-        if (minimal(64) && a.Cout % 128 == 0 && !batched) {
-          dim3 g((Mg + 63) / 64, a.Cout / 128, gz);
-          conv2_kernel<T, 64, 128, 2, 2, 2, KH, KW, S, P, EPI_SWAP | EPI_GNA><<<g, 256, 0, st>>>(a);
-          return;
-        }
-      throw std::logic_error("conv: conv_gna_ok promised an input-GroupNorm kernel");
-    }
-    if constexpr (KH == 1) if (a.lnf_cs) {
-      // Input LayerNorm folded in (conv_lnf_ok mirrors these two choices).
-      // (Swapped 64x128 tiles only. A 256x256 GEGLU | LNF tile existed in round 3; its fp16
-      // outputs depended on the batch composition and it was slower than the unfolded chain, so
-      // it was removed together with conv_lnf_ok's GEGLU case.)
-      if constexpr (sizeof(T) == 2) {
-        if (a.act != ACT_GEGLU && minimal(64) && a.Cout % 128 == 0) {
-          dim3 g((Mg + 63) / 64, a.Cout / 128, gz);
-          conv2_kernel<T, 64, 128, 2, 2, 2, KH, KW, S, P, EPI_SWAP | EPI_LNF><<<g, 256, 0, st>>>(a);
-          return;
-        }
-      }
-      throw std::logic_error("conv: conv_lnf_ok promised a folding kernel");
-    }
-    const int f2 = (KH == 1 && g_conv2_force32 > 0 && a.Ho > 1 && a.Wo > 1 && a.Ho * a.Wo <= 1024 && a.Ho * a.Wo >= 256 && a.ksplit <= 1 && a.act != ACT_GEGLU) ? g_conv2_force32 : g_conv2_force;
-    if constexpr (KH == 1) if (f2 > 0) {
-      switch (f2) {
-        case 1: DAC_V2(256, 128, 4, 2, 3, 512)
-        case 2: DAC_V2(128, 128, 2, 2, 2, 256)
-        case 3: DAC_V2(256, 128, 4, 2, 2, 512)
-        case 4: DAC_V2(128, 128, 2, 2, 3, 256)
-        case 5: {
-          dim3 g((Mg + 255) / 256, (a.Cout + 255) / 256, gz);
-          conv2_kernel<T, 256, 256, 4, 2, 2, KH, KW, S, P, EPI_MIN><<<g, 512, 0, st>>>(a);
-          return;
-        }
-        case 6: DAC_V2(128, 256, 2, 4, 2, 512)
-        case 7: DAC_V2(128, 64, 2, 2, 2, 256)
-        case 8: DAC_V2(64, 128, 2, 2, 2, 256)
-        case 9: DAC_V2(64, 64, 2, 2, 3, 256)
-        case 10: DAC_V2(128, 64, 2, 2, 3, 256)
-        case 11: DAC_V2(64, 128, 2, 2, 3, 256)
-        case 12: DAC_V2(64, 128, 2, 2, 4, 256)
-        case 13:
-          if constexpr (sizeof(T) == 2)
-            if (minimal(64) && a.Cout % 128 == 0) {
-              dim3 g((Mg + 63) / 64, a.Cout / 128, gz);
-              conv2_kernel<T, 64, 128, 2, 2, 3, KH, KW, S, P, EPI_SWAP><<<g, 256, 0, st>>>(a);
-              return;
-            }
-          DAC_V2(64, 128, 2, 2, 3, 256)
-        case 17:
-        case 18:
-        case 19:
-          if constexpr (sizeof(T) == 2)
-            if (minimal(128) && a.Cout % 128 == 0) {
-              // Deep rings (in-flight depth probe): 64x128 x 6 stages, 128x128 x 4 / 5 stages.
-              if (f2 == 17) conv2_kernel<T, 64, 128, 2, 2, 6, KH, KW, S, P, EPI_SWAP><<<dim3((Mg + 63) / 64, a.Cout / 128, gz), 256, 0, st>>>(a);
-              else if (f2 == 18) conv2_kernel<T, 128, 128, 2, 2, 4, KH, KW, S, P, EPI_SWAP><<<dim3((Mg + 127) / 128, a.Cout / 128, gz), 256, 0, st>>>(a);
-              else conv2_kernel<T, 128, 128, 2, 2, 5, KH, KW, S, P, EPI_SWAP><<<dim3((Mg + 127) / 128, a.Cout / 128, gz), 256, 0, st>>>(a);
-              return;
-            }
-          DAC_V2(64, 128, 2, 2, 2, 256)
-        case 14:
-        case 15:
-        case 16:
-          if constexpr (sizeof(T) == 2)
-            if (minimal(128) && a.Cout % 128 == 0) {
-              dim3 g((Mg + 127) / 128, a.Cout / 128, gz);
-              if (f2 == 14) conv2_kernel<T, 128, 128, 2, 2, 2, KH, KW, S, P, EPI_SWAP><<<g, 256, 0, st>>>(a);
-              else if (f2 == 15) conv2_kernel<T, 128, 128, 2, 2, 3, KH, KW, S, P, EPI_SWAP><<<g, 256, 0, st>>>(a);
-              else conv2_kernel<T, 64, 128, 2, 2, 4, KH, KW, S, P, EPI_SWAP><<<dim3((Mg + 63) / 64, a.Cout / 128, gz), 256, 0, st>>>(a);
-              return;
-            }
-          DAC_V2(64, 128, 2, 2, 2, 256)
-        default: break;
-      }
-    }
-    if constexpr (KH == 1) if (a.ksplit > 1 && a.part) {
-      // Split-K (conv_split_ok): 64x128 tiles, grid z = ksplit, then the reduce + epilogue pass.
-      if (a.ln_g || a.lnf_cs || a.gna_stats || batched || a.act == ACT_GEGLU)
-        throw std::logic_error("conv: epilogue feature without a kernel for this shape");
-      dim3 g((Mg + 63) / 64, (a.Cout + 127) / 128, a.ksplit);
-      conv2_kernel<T, 64, 128, 2, 2, 2, KH, KW, S, P, EPI_PART><<<g, 256, 0, st>>>(a);
-      conv_part_reduce<T>(a, st);
-      return;
-    }
-    if constexpr (KH == 1) if (a.K <= BKE) {
-      // One K tile (1x1 over 64 bf16 channels): no pipeline to fill, so a single small
-      // stage (128x64, 4 waves) keeps several blocks resident per CU and their load
-      // latencies overlap (measured best of 256x128 x {1,2,3} stages, 128x128, 128x64).
-      DAC_V2(128, 64, 2, 2, 1, 256)
-    }
-    if constexpr (KH == 1) if (a.Cout <= 64) DAC_V2(128, 64, 2, 2, 2, 256)
-    if (a.Cout <= 64) DAC_V2(256, 64, 4, 2, 3, 512)
-    if constexpr (KH == 1) {
-      // 1x1 / linear GEMMs (measured, tools/convbench 1x1 sweep): Cout <= 64 (K > 64) 128x64
-      // with 2 stages (above); GEGLU projections 128x256 (8 waves of 64x64, 2 stages); wide
-      // plain outputs 256x256 (8 waves of 64x128, 2 stages, minimal epilogue only: the
-      // general one spills at this tile); the rest 64x128 with 2 stages (4 waves of 32x64),
-      // which doubles the blocks of the small 32x32-level GEMMs over 128x128.
-      if (a.act == ACT_GEGLU) {
-        // Swapped tiles with the register GEGLU epilogue (weights in the w_gs order): no LDS
-        // staging of the fp32 tile, 16-byte stores straight from the accumulators.
-        if constexpr (sizeof(T) == 2)
-          if (a.w_gs && a.b_gs && rows_ok && !a.res1 && !a.res2 && !a.bbias && !a.ss && g_geglu_sw > 0) {
-            ConvArgs q = a;
-            q.w = a.w_gs; q.bias = a.b_gs;
-            const int cfg = g_conv2_force >= 20 && g_conv2_force <= 23 ? g_conv2_force - 19 : g_geglu_sw;
-            if (cfg == 1 && (batched || HWo % 256 == 0) && a.Cout % 256 == 0) {
-              conv2_kernel<T, 256, 256, 4, 4, 2, KH, KW, S, P, EPI_SWAP | EPI_GEGLU><<<dim3((Mg + 255) / 256, a.Cout / 256, gz), 1024, 0, st>>>(q);
-              return;
-            }
-            if (cfg == 2 && (batched || HWo % 128 == 0) && a.Cout % 256 == 0) {
-              conv2_kernel<T, 128, 256, 2, 4, 2, KH, KW, S, P, EPI_SWAP | EPI_GEGLU><<<dim3((Mg + 127) / 128, a.Cout / 256, gz), 512, 0, st>>>(q);
-              return;
-            }
-            if (cfg == 3 && (batched || HWo % 256 == 0) && a.Cout % 128 == 0) {
-              conv2_kernel<T, 256, 128, 4, 2, 2, KH, KW, S, P, EPI_SWAP | EPI_GEGLU><<<dim3((Mg + 255) / 256, a.Cout / 128, gz), 512, 0, st>>>(q);
-              return;
-            }
-            if (cfg == 4 && (batched || HWo % 128 == 0) && a.Cout % 128 == 0) {
-              conv2_kernel<T, 128, 128, 2, 2, 2, KH, KW, S, P, EPI_SWAP | EPI_GEGLU><<<dim3((Mg + 127) / 128, a.Cout / 128, gz), 256, 0, st>>>(q);
-              return;
-            }
-          }
-        // 256x256 tiles when they stay inside one image: half the LDS-DMA bytes per MFMA of
-        // the 128x256 tiles, whose per-stage refill the MFMAs could not cover.
-        if constexpr (sizeof(T) == 2)
-          if (rows_ok && !a.res1 && !a.res2 && !a.bbias && (batched || HWo % 256 == 0) && a.Cout % 256 == 0 &&
-              g_conv2_force == 0) {
-            dim3 g((Mg + 255) / 256, a.Cout / 256, gz);
-            conv2_kernel<T, 256, 256, 4, 2, 2, KH, KW, S, P, EPI_GEGLU><<<g, 512, 0, st>>>(a);
-            return;
-          }
-        DAC_V2(128, 256, 2, 4, 2, 512)
-      }
-      if (a.Cout >= 1024 && minimal(256)) {
-        dim3 g((Mg + 255) / 256, (a.Cout + 255) / 256, gz);
-        conv2_kernel<T, 256, 256, 4, 2, 2, KH, KW, S, P, EPI_MIN><<<g, 512, 0, st>>>(a);
-        return;
-      }
-      // bf16, whole tiles in one image, Cout a multiple of the tile: swapped operands +
-      // register epilogue (no LDS round trip).
-      if constexpr (sizeof(T) == 2)
-        if (minimal(64) && a.Cout % 128 == 0 && g_conv2_force == 0) {
-          dim3 g((Mg + 63) / 64, a.Cout / 128, gz);
-          conv2_kernel<T, 64, 128, 2, 2, 2, KH, KW, S, P, EPI_SWAP><<<g, 256, 0, st>>>(a);
-          return;
-        }
-      DAC_V2(64, 128, 2, 2, 2, 256)
-    }
-    if ((long)((Mg + 255) / 256) * ((a.Cout + 127) / 128) * gz >= 256) DAC_V2(256, 128, 4, 2, 3, 512)
-    DAC_V2(128, 128, 2, 2, 3, 256)
-#undef DAC_V2
-  }
-  if (a.Cout <= 16 && a.act != ACT_GEGLU) {
-    dim3 g((Mg + 255) / 256, (a.Cout + 15) / 16, gz);
-    conv_kernel<T, 256, 16, 4, 1, KH, KW, S, P><<<g, 256, 0, st>>>(a);
-  } else if (a.Cout <= 64) {
-    dim3 g((Mg + 255) / 256, (a.Cout + 63) / 64, gz);
-    conv_kernel<T, 256, 64, 4, 1, KH, KW, S, P><<<g, 256, 0, st>>>(a);
-  } else {
-    dim3 g((Mg + 127) / 128, (a.Cout + 127) / 128, gz);
-    conv_kernel<T, 128, 128, 2, 2, KH, KW, S, P><<<g, 256, 0, st>>>(a);
-  }
+  throw std::logic_error(std::string("conv: planned ") + conv_kind_name(p.kind) + " configuration is not instantiated");
 }
 
 

@@ -630,8 +630,7 @@ void conv_call(Run& r, const ConvW& cw, const void* x1, int ld1, int C1, const v
     for (int u = cw.wpc ? 2 : 1; u >= 1; --u) {
       ConvArgs q = a;
       q.w = u == 2 ? cw.wpc : cw.wph; q.K = (u == 2 ? 16 : 12) * cw.cin; q.uph = u;
-      if (!r.zero) q.zero = &q;                      // (dry runs carry no zero page)
-      if (conv_uph_ok(q)) {
+      if (conv_uph_ok(q, (int)sizeof(T))) {
         a.w = q.w; a.K = q.K; a.uph = u;
         fl = 2.0 * M * cw.cout * (u == 2 ? 4 : 6) * cw.cin_real;
         break;
@@ -648,7 +647,6 @@ void conv_call(Run& r, const ConvW& cw, const void* x1, int ld1, int C1, const v
       (long)a.Ho * a.Wo <= split_px && a.Ho > 1) {
     ConvArgs q = a;
     q.w2 = nullptr; q.bias2 = nullptr; q.y2 = nullptr; q.w2_dual = 0; q.ldy2 = 0;
-    if (!r.zero) q.zero = &q;
     ks3 = conv3_split_k(q, (int)sizeof(T), g_splitk);
   }
   bool fused = false;
@@ -673,9 +671,7 @@ void conv_call(Run& r, const ConvW& cw, const void* x1, int ld1, int C1, const v
   const long srows = e.split_rows > 0 ? e.split_rows
                      : (split1 && g_splitk > 1 && a.Ho > 1 && a.Wo > 1 && (long)a.Ho * a.Wo <= 1024) ? (long)a.Ho * a.Wo : 0;
   if (srows > 0 && cw.kh == 1 && cw.kw == 1 && stride == 1 && pad == 0 && !use8 && !e.fuse1x1) {
-    ConvArgs q = a;
-    if (!r.zero) q.zero = &q;
-    const int ks = conv_split_k(q, (int)sizeof(T), srows);
+    const int ks = conv_split_k(a, (int)sizeof(T), srows);
     if (ks > 1) {
       a.ksplit = ks;
       a.part = r.alloc<float>((size_t)ks * (size_t)M * cw.cout);
@@ -691,7 +687,6 @@ void conv_call(Run& r, const ConvW& cw, const void* x1, int ld1, int C1, const v
     return;
   }
   if (!cw.w) throw Error(DAC_E_STATE, "conv weight not loaded");
-  // (Dry runs carry no zero page; the engine chose these paths with the same predicates.)
   if (a.lnf_cs && !conv_lnf_ok(a, (int)sizeof(T))) throw Error(DAC_E_STATE, "conv: LN fold requested on a shape without a folding kernel");
   if (a.gna_stats && !conv_gna_ok(a, (int)sizeof(T))) throw Error(DAC_E_STATE, "conv: GroupNorm A path requested on a shape without such a kernel");
   if (a.ys8 && !conv_q8out_ok(a)) throw Error(DAC_E_STATE, "conv: fp8 output requested on a shape without such a kernel");
@@ -1192,7 +1187,6 @@ struct UNetNet {
       // writes it as e4m3 + per-(pixel, 32-channel) exponents and block2 runs on the block-scaled
       // MFMA (conv3q.hip). Shapes without both kernels keep the 16-bit pair.
       ConvArgs q = conv_args(r, rb.c1, xa, Ca, Ca, xb, Cb, B, H, W, 0, 1, 1, h1, 64, e1);
-      q.zero = &q;                                // (dry runs carry no zero page)
       ConvArgs q2 = q;
       q2.x1 = h1; q2.x2 = nullptr; q2.xs8 = reinterpret_cast<const uint8_t*>(&q); q2.ld1 = q2.C1 = q2.Cin = 64;
       q2.K = 576; q2.ss = nullptr; q2.res1 = res; q2.ldr1 = rb.has_res ? rb.dout : Ca; q2.y2 = nullptr; q2.w2 = nullptr;
@@ -1330,12 +1324,12 @@ struct UNetNet {
   // The dispatcher has an LN-folding kernel for this 1x1 GEMM shape (conv_lnf_ok).
   static bool gna_fits(int C, int Cout, int HW) {
     ConvArgs a{};
-    a.zero = &a; a.Cin = a.C1 = a.K = C; a.Cout = a.ldy = Cout; a.gna_groups = 32; a.Ho = HW; a.Wo = 1;
+    a.Cin = a.C1 = a.K = C; a.Cout = a.ldy = Cout; a.gna_groups = 32; a.Ho = HW; a.Wo = 1;
     return fold_on(8) && conv_gna_ok(a, (int)sizeof(T));
   }
   static bool lnf_fits(int Cin, int Cout, int act, int HW) {
     ConvArgs a{};
-    a.zero = &a; a.Cin = a.C1 = Cin; a.Cout = Cout; a.act = act; a.ldy = act == ACT_GEGLU ? Cout / 2 : Cout;
+    a.Cin = a.C1 = Cin; a.Cout = Cout; a.act = act; a.ldy = act == ACT_GEGLU ? Cout / 2 : Cout;
     a.Ho = HW; a.Wo = 1;
     return conv_lnf_ok(a, (int)sizeof(T));
   }

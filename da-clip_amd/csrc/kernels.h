@@ -131,9 +131,11 @@ size_t layernorm_gnstats_ws_floats(int B, int HW, int groups);
 // The dispatcher can fuse a_w2/y2 into this 3x3 conv (bf16 v4 256x64 swapped-operand tiles).
 bool conv_res_fusable(const ConvArgs& a);
 
+// (The zero page, ConvArgs::zero, is a launch-time requirement the dispatcher checks: no fit
+// function below reads it, so the engine can ask before the page exists.)
 // Shapes served by the weight-stationary 3x3 kernel (conv_impl.h conv3w_kernel, 16-bit types).
 inline bool conv3w_ok(const ConvArgs& a) {
-  return a.Cin == 64 && a.Cout == 64 && a.K == 576 && a.cwrap == 0 && !a.y2 && (!a.ss || (a.ss_ld % 4 == 0 && ((uintptr_t)a.ss & 15) == 0)) && a.zero && a.amode == 0 && a.w_bstride == 0 &&
+  return a.Cin == 64 && a.Cout == 64 && a.K == 576 && a.cwrap == 0 && !a.y2 && (!a.ss || (a.ss_ld % 4 == 0 && ((uintptr_t)a.ss & 15) == 0)) && a.amode == 0 && a.w_bstride == 0 &&
          !a.ln_g && (a.act == ACT_NONE || a.act == ACT_SILU) && a.Wo >= 64 && a.Wo % 64 == 0 &&
          (a.C1 >= a.Cin || a.C1 % 32 == 0) && a.ldy % 8 == 0 && a.ld1 % 8 == 0 &&
          (a.C1 >= a.Cin || a.ld2 % 8 == 0) && (!a.res1 || a.ldr1 % 8 == 0) && !a.res2 && !a.bbias && !(a.ss && a.res1);   // (epi_regs16 PRE)
@@ -167,8 +169,6 @@ void conv3r(const ConvArgs& a, hipStream_t st);
 // init_conv (7x7, Cin 8 row-tap layout, Cout 64, bf16 / f16, plain or split-precision weights):
 // weight-stationary persistent kernel (conv_edge.hip).
 bool conv7_ok(const ConvArgs& a);
-// v6 2-D halo 3x3 kernel (conv_impl.h conv3h_kernel) takes this conv (conv.hip).
-bool conv3h_ok(const ConvArgs& a, int elem_bytes);
 template <typename T>
 void conv7(const ConvArgs& a, hipStream_t st);
 // final_conv (3x3, Cin 64 -> Cout <= 4, bf16 / f16, plain or split-precision weights, Wo % 64 == 0):
@@ -209,7 +209,7 @@ int conv3_split_k(const ConvArgs& a, int elem_bytes, int ks);
 template <typename T>
 void conv_part_reduce(const ConvArgs& a, hipStream_t st);
 // Row-phase upsample conv (ConvArgs::uph): the dispatcher has the kernel for this conv.
-bool conv_uph_ok(const ConvArgs& a);
+bool conv_uph_ok(const ConvArgs& a, int elem_bytes);
 bool conv3q_ok(const ConvArgs& a);
 template <typename T>
 void conv3q(const ConvArgs& a, const uint8_t* q8w, const uint8_t* q8s, hipStream_t st);

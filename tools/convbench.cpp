@@ -3,6 +3,7 @@
 //   force-list: comma-separated 3x3 kernel choices (-1 built-in, 0 v3, k>0 v4 config k)
 //   prints per-shape time and TFLOP/s for bf16; with "check" the inputs are random and every
 //   output is compared with a naive reference conv (fp32 accumulate, same epilogue).
+//        convbench plan FILE: the kernel selection for each conv call of FILE, no GPU needed.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -11,6 +12,7 @@
 #include <vector>
 #include <algorithm>
 #include "../da-clip_amd/csrc/kernels.h"
+#include "../da-clip_amd/csrc/conv_plan.h"
 
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e)); exit(1);} } while (0)
 using namespace dac;
@@ -803,8 +805,8 @@ template <typename E> static int uph_check(int iters, const char* tn) {
     u.w = dp; u.K = 12 * C; u.uph = 1; u.y = dy1;
     ConvArgs u2 = a;
     u2.w = dq; u2.K = 16 * C; u2.uph = 2; u2.y = dy2;
-    const bool col = conv_uph_ok(u2);
-    if (!conv_uph_ok(u)) { printf("%s %-28s not eligible\n", tn, sh.name); ++fails; continue; }
+    const bool col = conv_uph_ok(u2, 2);
+    if (!conv_uph_ok(u, 2)) { printf("%s %-28s not eligible\n", tn, sh.name); ++fails; continue; }
     conv<E>(a, 3, 3, 1, 1, 0);
     conv<E>(u, 3, 3, 1, 1, 0);
     if (col) conv<E>(u2, 3, 3, 1, 1, 0);
@@ -1399,7 +1401,83 @@ template <typename E> static int conv_shapes(int argc, char** argv, const char* 
   return 0;
 }
 
+// `convbench plan FILE`: the kernel selection (csrc/conv_plan.h) for each line of FILE, with no
+// HIP call. A line is space-separated key=value pairs: the conv (kh kw s p es), the ConvArgs
+// fields, 0/1 flags for its pointers (x2, 2 = the same tensor as x1; ss res1 res2 bbias ln lnf gna y2 w2 b2 ys8 gs; ssmis /
+// biasmis = not 16-byte aligned), ks = ksplit, and the knobs (f3 f2 f32 buf st gsw c3wbuf ncu;
+// defaults, not the environment). Prints the plan, whether the chosen kernel's own fit function
+// accepts the arguments, and the engine's predicates for the requests the line carries.
+static int plan_mode(const char* path) {
+  FILE* f = path ? fopen(path, "r") : nullptr;
+  if (!f) { fprintf(stderr, "usage: convbench plan FILE\n"); return 2; }
+  alignas(16) static char mem[64];
+  char line[2048];
+  while (fgets(line, sizeof line, f)) {
+    if (line[0] == '#' || line[0] == '\n') continue;
+    ConvArgs a{};
+    a.x1 = mem;
+    ConvKnobs k;
+    int kh = 3, kw = 3, s = 1, p = 1, es = 2;
+    for (char* t = strtok(line, " \n"); t; t = strtok(nullptr, " \n")) {
+      char* eq = strchr(t, '=');
+      if (!eq) continue;
+      *eq = 0;
+      const int v = atoi(eq + 1);
+      const void* ptr = v ? mem : nullptr;
+#define KEY(name, stmt) if (!strcmp(t, name)) { stmt; continue; }
+      KEY("kh", kh = v) KEY("kw", kw = v) KEY("s", s = v) KEY("p", p = v) KEY("es", es = v)
+      KEY("B", a.B = v) KEY("Hs", a.Hs = v) KEY("Ws", a.Ws = v) KEY("up", a.up = v) KEY("Ho", a.Ho = v) KEY("Wo", a.Wo = v)
+      KEY("Cin", a.Cin = v) KEY("C1", a.C1 = v) KEY("x2", a.x2 = v == 2 ? a.x1 : v ? mem + 16 : nullptr) KEY("ld1", a.ld1 = v) KEY("ld2", a.ld2 = v)
+      KEY("Cout", a.Cout = v) KEY("K", a.K = v) KEY("ldy", a.ldy = v) KEY("act", a.act = v) KEY("amode", a.amode = v)
+      KEY("wb", a.w_bstride = v) KEY("cwrap", a.cwrap = v) KEY("ss", a.ss = (const float*)ptr) KEY("ss_ld", a.ss_ld = v)
+      KEY("ssmis", if (v && a.ss) a.ss = (const float*)(mem + 4)) KEY("biasmis", if (v) a.bias = (const float*)(mem + 4))
+      KEY("res1", a.res1 = ptr) KEY("ldr1", a.ldr1 = v) KEY("res2", a.res2 = ptr) KEY("ldr2", a.ldr2 = v)
+      KEY("bbias", a.bbias = (const float*)ptr) KEY("ln", a.ln_g = (const float*)ptr) KEY("lnf", a.lnf_cs = (const float*)ptr)
+      KEY("gna", a.gna_stats = (const float*)ptr) KEY("groups", a.gna_groups = v) KEY("y2", a.y2 = v ? mem : nullptr)
+      KEY("w2", a.w2 = ptr) KEY("w2d", a.w2_dual = v) KEY("b2", a.bias2 = (const float*)ptr) KEY("ldy2", a.ldy2 = v)
+      KEY("ys8", a.ys8 = v ? (uint8_t*)mem : nullptr) KEY("uph", a.uph = v) KEY("ks", a.ksplit = v)
+      KEY("gs", a.w_gs = ptr; a.b_gs = (const float*)ptr)
+      KEY("f3", k.conv3_force = v) KEY("f2", k.conv2_force = v) KEY("f32", k.conv2_force32 = v) KEY("buf", k.conv3_buf = v)
+      KEY("st", k.c3i_st = v) KEY("gsw", k.geglu_sw = v) KEY("c3wbuf", k.c3w_buf = v) KEY("ncu", k.ncu = v)
+#undef KEY
+      fprintf(stderr, "convbench plan: unknown key %s\n", t);
+      return 2;
+    }
+    const ConvPlan q = conv_plan(a, kh, kw, s, p, es, k);
+    bool fit = true;
+    switch (q.kind) {
+      case CONV_7: fit = conv7_ok(a); break;
+      case CONV_3N: fit = conv3n_ok(a); break;
+      case CONV_DOWN: fit = conv_down_ok(a); break;
+      case CONV_3R: fit = conv3r_ok(a); break;
+      case CONV_3W: fit = conv3w_ok(a) && (!q.buffer_dma || conv3w_buf_fit(a)); break;
+      case CONV_3I: fit = conv3i_fit(a, es, q.BM, q.WGM, q.CK, q.fl); break;
+      case CONV_3: case CONV_3_SPLIT: fit = conv3_rw(a, q.BM) == q.RW && q.RW > 0 && (!q.buffer_dma || conv3_buf_fit(a, es)); break;
+      case CONV_2: fit = (!(q.epi & EPI_LNF) || conv2_lnf_fit(a)) && (!(q.epi & EPI_GNA) || conv2_gna_fit(a)) &&
+                         (!q.buffer_dma || conv2_buf_fit(a, es)); break;
+      default: break;
+    }
+    // The engine's predicates (3x3: res / q8 (16-bit only) / uph / sp, 1x1: lnf / gna), asked the way the engine
+    // asks them: before the request is set.
+    conv_knobs() = k;
+    char pr[96] = "";
+    ConvArgs h = a;
+    if (a.y2 && kh == 3 && es == 2) snprintf(pr + strlen(pr), 16, " res=%d", conv_res_fusable(a));
+    if (a.ys8 && kh == 3 && es == 2) { h = a; h.ys8 = nullptr; snprintf(pr + strlen(pr), 16, " q8=%d", conv_q8out_ok(h)); }
+    if (a.uph && kh == 3) snprintf(pr + strlen(pr), 16, " uph=%d", conv_uph_ok(a, es));
+    if (a.lnf_cs && kh == 1) { h = a; h.lnf_cs = nullptr; snprintf(pr + strlen(pr), 16, " lnf=%d", conv_lnf_ok(h, es)); }
+    if (a.gna_stats && kh == 1) { h = a; h.gna_stats = nullptr; snprintf(pr + strlen(pr), 16, " gna=%d", conv_gna_ok(h, es)); }
+    if (a.ksplit > 1 && kh == 3) { h = a; h.ksplit = 0; snprintf(pr + strlen(pr), 16, " sp=%d", conv3_split_ok(h, es)); }
+    printf("kind=%s tile=%dx%d wg=%dx%d ck=%d st=%d fl=%d epi=%d dma=%s gs=%d rw=%d grid=%u,%u,%u thr=%d delay=%d label=%d serves=%d fit=%d%s why=%s\n",
+           conv_kind_name(q.kind), q.BM, q.BN, q.WGM, q.WGN, q.CK, q.ST, q.fl, q.epi, q.buffer_dma ? "buf" : "flat", q.w_gs,
+           q.RW, q.gx, q.gy, q.gz, q.threads, q.delay, q.label, conv_plan_serves(q), fit, pr, q.why_not ? q.why_not : "-");
+  }
+  fclose(f);
+  return 0;
+}
+
 int main(int argc, char** argv) {
+  if (argc > 1 && !strcmp(argv[1], "plan")) return plan_mode(argc > 2 ? argv[2] : nullptr);
   if (argc > 1 && !strcmp(argv[1], "la")) return la_bench(argc > 2 ? atoi(argv[2]) : 20, argc > 3 ? atof(argv[3]) : 0.f);
   if (argc > 1 && !strcmp(argv[1], "st")) return c3i_st_check(argc > 2 ? atoi(argv[2]) : 20);
   if (argc > 1 && !strcmp(argv[1], "gsw")) return gsw_check(argc > 2 ? atoi(argv[2]) : 20);
