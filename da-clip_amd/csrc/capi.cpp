@@ -8,6 +8,7 @@
 #include <set>
 
 #include "engine.h"
+#include "conv_plan.h"
 
 struct dac_handle {
   int device = 0;
@@ -400,6 +401,106 @@ int dac_op_linear_attention_weff(const void* qkv, const float* wout, void* weff,
   const hipError_t e = hipGetLastError();
   const hipError_t es = hipStreamSynchronize(st);
   return e == hipSuccess && es == hipSuccess ? DAC_OK : DAC_E_HIP;
+}
+
+namespace {
+
+// The three selection knobs dac_op_conv may override for one call (the CU count stays).
+struct KnobOverride {
+  dac::ConvKnobs& k = dac::conv_knobs();
+  const int s3 = k.conv3_force, s2 = k.conv2_force, s32 = k.conv2_force32;
+  explicit KnobOverride(const dac_conv_desc& d) {
+    if (d.conv3_force != DAC_CONV_KEEP) k.conv3_force = d.conv3_force;
+    if (d.conv2_force != DAC_CONV_KEEP) k.conv2_force = d.conv2_force;
+    if (d.conv2_force32 != DAC_CONV_KEEP) k.conv2_force32 = d.conv2_force32;
+  }
+  ~KnobOverride() { k.conv3_force = s3; k.conv2_force = s2; k.conv2_force32 = s32; }
+};
+
+// Descriptor + pointers -> ConvArgs (y, zero and part are filled in by the caller). False: an
+// argument the kernels would index out of bounds with, or that no layer has.
+bool conv_op_args(const dac_conv_desc& d, const void* x1, const void* x2, const void* w, const float* bias,
+                  const float* ss, const void* res1, const void* res2, const float* bbias, const void* w_gs,
+                  const float* b_gs, dac::ConvArgs& a, int& stride, int& pad) {
+  if (d.dtype != DAC_F32 && d.dtype != DAC_BF16 && d.dtype != DAC_F16) return false;
+  if (d.kh != 1 && d.kh != 3 && d.kh != 4 && d.kh != 7) return false;
+  if (!x1 || !w) return false;
+  const int es = d.dtype == DAC_F32 ? 4 : 2, VE = 16 / es;
+  stride = d.kh == 4 ? 2 : 1;
+  pad = d.kh == 3 || d.kh == 4 ? 1 : d.kh == 7 ? 3 : 0;
+  const long LIM = 1 << 24;
+  if (d.B < 1 || d.Hs < 1 || d.Ws < 1 || d.B > LIM || d.Hs > LIM || d.Ws > LIM || (d.up != 0 && d.up != 1) ||
+      (d.up && d.kh != 3))
+    return false;
+  const int Hin = d.up ? 2 * d.Hs : d.Hs, Win = d.up ? 2 * d.Ws : d.Ws;
+  if (Hin + 2 * pad < d.kh || Win + 2 * pad < d.kh || (d.kh == 4 && ((Hin | Win) & 1))) return false;
+  const int Ho = (Hin + 2 * pad - d.kh) / stride + 1, Wo = (Win + 2 * pad - d.kh) / stride + 1;
+  if ((long)d.B * Ho * Wo > ((long)1 << 30)) return false;
+  if (d.Cin < VE || d.Cin % VE || d.Cin > LIM || d.C1 < 1 || d.Cout < 1 || d.Cout > LIM || d.cwrap < 0 || d.ksplit < 0 ||
+      d.ksplit > 64)
+    return false;
+  if (d.act < dac::ACT_NONE || d.act > dac::ACT_GEGLU || (d.act == dac::ACT_GEGLU && (d.kh != 1 || d.Cout % 32)))
+    return false;
+  // K: [kh][kw][Cin], or the 7x7 row-tap layout (kw padded to 8; cwrap = 1: [hi rows | lo rows]).
+  const bool rowtap = d.kh == 7 && d.Cin == 8 && d.K == (d.cwrap ? 2 : 1) * 7 * 8 * 8 && d.cwrap <= 1;
+  if (!rowtap && (d.K != d.kh * d.kh * d.Cin || d.cwrap >= d.Cin || (d.cwrap && d.cwrap * 2 != d.Cin))) return false;
+  // Channels [0, C1) from x1, the rest (up to the wrap) from x2.
+  const int Cread = d.cwrap > 1 ? d.cwrap : d.Cin;
+  if (d.C1 < Cread && (!x2 || d.ld2 < Cread - d.C1)) return false;
+  if (d.ld1 < (d.C1 < Cread ? d.C1 : Cread)) return false;
+  const int Cy = d.act == dac::ACT_GEGLU ? d.Cout / 2 : d.Cout;
+  if (d.ldy < Cy || (res1 && d.ldr1 < Cy) || (res2 && d.ldr2 < Cy) || (ss && d.ss_ld < 0) || (bbias && d.bb_ld < 0))
+    return false;
+  a = dac::ConvArgs{};
+  a.x1 = x1; a.x2 = x2; a.ld1 = d.ld1; a.ld2 = d.ld2; a.C1 = d.C1; a.Cin = d.Cin;
+  a.Hs = d.Hs; a.Ws = d.Ws; a.up = d.up; a.B = d.B; a.Ho = Ho; a.Wo = Wo; a.Cout = d.Cout; a.K = d.K;
+  a.w = w; a.bias = bias; a.ss = ss; a.ss_ld = d.ss_ld; a.res1 = res1; a.ldr1 = d.ldr1; a.res2 = res2;
+  a.ldr2 = d.ldr2; a.bbias = bbias; a.bb_ld = d.bb_ld; a.ldy = d.ldy; a.act = d.act; a.cwrap = d.cwrap;
+  a.ksplit = d.ksplit > 1 ? d.ksplit : 0;
+  if (d.act == dac::ACT_GEGLU) { a.w_gs = w_gs; a.b_gs = b_gs; }
+  return true;
+}
+
+}  // namespace
+
+int dac_op_conv(const dac_conv_desc* d, const void* x1, const void* x2, const void* w, const float* bias,
+                const float* ss, const void* res1, const void* res2, const float* bbias, const void* w_gs,
+                const float* b_gs, void* y, int* plan_out, void* stream) {
+  if (!d) return DAC_E_ARG;
+  dac::ConvArgs a;
+  int stride = 1, pad = 0;
+  if (!conv_op_args(*d, x1, x2, w, bias, ss, res1, res2, bbias, w_gs, b_gs, a, stride, pad)) return DAC_E_ARG;
+  const int es = d->dtype == DAC_F32 ? 4 : 2;
+  KnobOverride knobs(*d);
+  // Planning never touches HIP (plan-only calls and every refusal stay off the device); a launch
+  // then plans again with the device's CU count, as conv_dispatch does.
+  dac::ConvPlan p = dac::conv_plan(a, d->kh, d->kh, stride, pad, es, dac::conv_knobs());
+  if (p.kind == dac::CONV_NONE) return DAC_E_ARG;
+  if (y) p = dac::conv_plan(a, d->kh, d->kh, stride, pad, es, dac::conv_launch_knobs());
+  if (plan_out) {
+    const int v[DAC_CONV_PLAN_N] = {(int)p.kind, p.BM, p.BN, p.ST, p.epi, p.fl, p.buffer_dma ? 1 : 0, p.label};
+    std::copy(v, v + DAC_CONV_PLAN_N, plan_out);
+  }
+  if (!y) return DAC_OK;
+  const hipStream_t st = (hipStream_t)stream;
+  DevBuf zero, part;
+  if (!zero.alloc(256)) return DAC_E_NOMEM;
+  if (a.ksplit > 1 && !part.alloc((size_t)a.ksplit * a.B * a.Ho * a.Wo * a.Cout * sizeof(float))) return DAC_E_NOMEM;
+  hipError_t e = hipMemsetAsync(zero.p, 0, 256, st);
+  a.y = y; a.zero = zero.p; a.part = (float*)part.p;
+  if (e == hipSuccess) {
+    try {
+      if (d->dtype == DAC_BF16) dac::conv<__bf16>(a, d->kh, d->kh, stride, pad, st);
+      else if (d->dtype == DAC_F16) dac::conv<_Float16>(a, d->kh, d->kh, stride, pad, st);
+      else dac::conv<float>(a, d->kh, d->kh, stride, pad, st);
+      e = hipGetLastError();
+    } catch (const std::exception&) {
+      (void)hipStreamSynchronize(st);
+      return DAC_E_ARG;
+    }
+  }
+  const hipError_t es2 = hipStreamSynchronize(st);
+  return e == hipSuccess && es2 == hipSuccess ? DAC_OK : DAC_E_HIP;
 }
 
 size_t dac_image_metrics_workspace(int B, int C, int H, int W, int crop_border) {

@@ -408,10 +408,11 @@ ConvPlan Sel::select() const {
     if (conv7_ok(a)) return own(CONV_7);
     if (a.Cin == 8 && a.K == (a.cwrap ? 2 : 1) * 7 * 8 * 8 && a.amode == 0 && a.w_bstride == 0 && !a.x2)
       return tile(CONV_2, 256, 64, 4, 2, 128, 3, EPI_ALL, (M + 255) / 256, (a.Cout + 63) / 64, 1);
-    // cwrap = 1 here means the row-tap dual layout (kernel rows wrap); the generic loaders read
-    // a nonzero cwrap as a channel wrap instead, so no other kernel may take it.
-    if (a.cwrap) return none("7x7 row-tap dual layout without its kernel");
   }
+  // cwrap = 1 here means the row-tap dual layout (kernel rows wrap), and K = 7 x 8 x Cin its
+  // padded kernel rows; the generic loaders read a nonzero cwrap as a channel wrap and K as
+  // [7][7][Cin], so no other kernel (of any element type) may take either.
+  if (kh == 7 && (a.cwrap || a.K != 49 * a.Cin)) return none("7x7 row-tap layout without its kernel");
   if (v2ok) return v2();
   if (a.Cout <= 16 && a.act != ACT_GEGLU) return tile(CONV_1, 256, 16, 4, 1, 128, 1, EPI_ALL, (Mg + 255) / 256, (a.Cout + 15) / 16, gz);
   if (a.Cout <= 64) return tile(CONV_1, 256, 64, 4, 1, 128, 1, EPI_ALL, (Mg + 255) / 256, (a.Cout + 63) / 64, gz);

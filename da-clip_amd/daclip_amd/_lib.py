@@ -40,7 +40,8 @@ EXPORTS = ["dac_create", "dac_destroy", "dac_set_weight", "dac_finalize_weights"
            "dac_profile_read", "dac_profile_mode", "dac_profile_launch", "dac_profile_graph_ms",
            "dac_op_attention", "dac_image_metrics_workspace", "dac_image_metrics", "dac_last_error",
            "dac_sde_reverse_tiled", "dac_op_tile_blend", "dac_op_linear_attention",
-           "dac_op_linear_attention_weff"]
+           "dac_op_linear_attention_weff", "dac_op_conv"]
+DAC_CONV_KEEP, DAC_CONV_PLAN_N = -1000, 8
 
 
 class DacConfig(ctypes.Structure):
@@ -54,6 +55,13 @@ class DacConfig(ctypes.Structure):
                 ("text", ctypes.c_int), ("context_length", ctypes.c_int), ("vocab_size", ctypes.c_int),
                 ("text_width", ctypes.c_int), ("text_heads", ctypes.c_int), ("text_layers", ctypes.c_int),
                 ("unet_scale_half", ctypes.c_int), ("unet_st_from", ctypes.c_int)]
+
+
+class DacConvDesc(ctypes.Structure):
+    """dac_conv_desc (include/daclip_hip.h): one conv launch for dac_op_conv."""
+    _fields_ = [(n, ctypes.c_int) for n in (
+        "dtype", "kh", "B", "Hs", "Ws", "up", "C1", "Cin", "ld1", "ld2", "Cout", "K", "ldy", "act", "cwrap",
+        "ksplit", "ss_ld", "ldr1", "ldr2", "bb_ld", "conv3_force", "conv2_force", "conv2_force32")]
 
 
 _lib = None
@@ -98,6 +106,7 @@ def lib() -> ctypes.CDLL:
         "dac_op_attention": (I, [P, P, I, I, I, I, I, P]),
         "dac_op_linear_attention": (I, [P, P, P, P, P, P, I, I, I, I, F, P]),
         "dac_op_linear_attention_weff": (I, [P, P, P, I, I, I, I, F, P]),
+        "dac_op_conv": (I, [ctypes.POINTER(DacConvDesc), P, P, P, P, P, P, P, P, P, P, P, ctypes.POINTER(I), P]),
         "dac_image_metrics_workspace": (ctypes.c_size_t, [I, I, I, I, I]),
         "dac_image_metrics": (I, [P, P, I, I, I, I, I, P, P, P, P, P]),
         "dac_last_error": (ctypes.c_char_p, [P]),

@@ -259,6 +259,47 @@ int dac_op_linear_attention(const void* x, const void* wqkv, const float* wout, 
 int dac_op_linear_attention_weff(const void* qkv, const float* wout, void* weff, int B, int HW, int C,
                                  int dtype, float hw_scale, void* stream);
 
+/* Op-level test hook: ONE conv / linear launch exactly as the dispatcher makes it (csrc/kernels.h
+ * ConvArgs, csrc/conv_plan.h), handle-less: the caller owns every tensor, all on the current
+ * device.   y[m, n] = epi(sum_k A[m, k] W[n, k]),  m = (b, oh, ow),  k = (kh, kw, ci)
+ * with A the zero-padded (up = 1: 2x nearest-upsampled) NHWC input, channels [0, C1) from x1 (row
+ * pitch ld1) and [C1, Cin) from x2 (ld2); epilogue +bias -> *(1 + scale) + shift -> act -> +res1 ->
+ * +res2 -> +bbias. kh in {1, 3, 4, 7} fixes the window: 1x1 s1 p0, 3x3 s1 p1, 4x4 s2 p1, 7x7 s1 p3.
+ * x1, x2, w, res1, res2, w_gs, y are in `dtype` (DAC_F32 / DAC_BF16 / DAC_F16); bias [Cout],
+ * ss (scale [b*ss_ld + n], shift [b*ss_ld + Cout + n]), bbias [b*bb_ld + n] and b_gs are fp32.
+ * w is [Cout][K] in the packed layout the kernels read (engine.cpp Packer): K = kh*kw*Cin, the
+ * 7x7 row-tap layout with kw padded to 8 (K = 7*8*Cin, twice that with cwrap = 1 for [hi rows |
+ * lo rows]), or [hi Cin | lo Cin] per tap over an input read twice (x2 = x1, or cwrap = Cin / 2).
+ * act: 0 none, 1 SiLU, 2 GELU, 3 GEGLU (w in the 16-row interleaved order, y has Cout / 2
+ * columns; w_gs / b_gs: the same in the swapped-tile order, or null). ksplit > 1: split-K over
+ * that many K ranges into an fp32 workspace the hook owns, then the reduce + epilogue pass.
+ * conv3_force / conv2_force / conv2_force32: the selection knobs of csrc/conv_plan.h for this
+ * call only (DAC_CONV_KEEP: leave the process's value); restored before the hook returns.
+ * plan_out (DAC_CONV_PLAN_N ints, or null) receives the plan: kind (ConvKind), BM, BN, ST, epi,
+ * fl, buffer_dma, label.
+ * y == NULL: plan-only. plan_out is filled from the selection and nothing else happens: no HIP
+ * call, so this mode works without a GPU (pointers are only tested for null / alignment).
+ * Otherwise the hook owns the zero page and the split-K workspace, runs on `stream`,
+ * synchronises it and frees its scratch on every path.
+ * DAC_E_ARG, before any device work: a null descriptor, x1 or w; a dtype, kh, act or dimension
+ * outside the above (B, Hs, Ws, Cin, Cout, K, ld*, ldy < 1 where used; Cin not a multiple of the
+ * 16-byte vector; ksplit < 0); C1 < Cin without x2; res1 / res2 with a pitch below the output
+ * width, ss / bbias with a negative one; or arguments for which the selection has no kernel
+ * (kind 0). */
+typedef struct dac_conv_desc {
+  int dtype, kh;
+  int B, Hs, Ws, up;
+  int C1, Cin, ld1, ld2;
+  int Cout, K, ldy;
+  int act, cwrap, ksplit;
+  int ss_ld, ldr1, ldr2, bb_ld;
+  int conv3_force, conv2_force, conv2_force32;
+} dac_conv_desc;
+enum { DAC_CONV_KEEP = -1000, DAC_CONV_PLAN_N = 8 };
+int dac_op_conv(const dac_conv_desc* d, const void* x1, const void* x2, const void* w, const float* bias,
+                const float* ss, const void* res1, const void* res2, const float* bbias, const void* w_gs,
+                const float* b_gs, void* y, int* plan_out, void* stream);
+
 /* Evaluation metrics of config/daclip-sde/test.py:131-196 on the device, handle-less (the
  * caller owns all memory; everything on the current device). out / gt: fp32 [B,C,H,W] RGB,
  * C in {1, 3}. out_bytes / gt_bytes: uint8 [B,H,W,C], BGR for C = 3, what util.tensor2img

@@ -68,6 +68,44 @@ int main() {
   EXPECT(dac_op_linear_attention_weff(dummy, dummy, dummy, 1, 64, 32, DAC_BF16, 0.f, nullptr) == DAC_E_ARG);
   EXPECT(dac_op_linear_attention_weff(dummy, dummy, dummy, 1, 64, 256, DAC_F32, 0.f, nullptr) == DAC_E_ARG);
   EXPECT(dac_op_linear_attention_weff(dummy, dummy, dummy, 1, 64, 64, DAC_F16, -0.5f, nullptr) == DAC_E_ARG);
+  // dac_op_conv: a null descriptor / input / weight, bad dtypes, windows and dimensions, a second
+  // source that is missing, and arguments no kernel serves are refused before any device work;
+  // with y == NULL a valid call only plans (no HIP call), so it runs here too.
+  {
+    dac_conv_desc cd;
+    std::memset(&cd, 0, sizeof cd);
+    cd.dtype = DAC_BF16; cd.kh = 1; cd.B = 2; cd.Hs = 8; cd.Ws = 8; cd.C1 = cd.Cin = cd.ld1 = 64;
+    cd.Cout = cd.ldy = 128; cd.K = 64;
+    cd.conv3_force = cd.conv2_force = cd.conv2_force32 = DAC_CONV_KEEP;
+    int plan[DAC_CONV_PLAN_N] = {0};
+    auto call = [&](const dac_conv_desc& q, const void* x1, const void* x2, const void* w, void* y) {
+      return dac_op_conv(&q, x1, x2, w, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, y, plan, nullptr);
+    };
+    EXPECT(dac_op_conv(nullptr, dummy, nullptr, dummy, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                       dummy, plan, nullptr) == DAC_E_ARG);
+    EXPECT(call(cd, nullptr, nullptr, dummy, dummy) == DAC_E_ARG);
+    EXPECT(call(cd, dummy, nullptr, nullptr, dummy) == DAC_E_ARG);
+    EXPECT(call(cd, dummy, nullptr, dummy, nullptr) == DAC_OK && plan[0] > 0 && plan[1] > 0);   // plan-only
+    dac_conv_desc q = cd;
+    q.dtype = DAC_FP8; EXPECT(call(q, dummy, nullptr, dummy, dummy) == DAC_E_ARG);
+    q = cd; q.dtype = 99; EXPECT(call(q, dummy, nullptr, dummy, dummy) == DAC_E_ARG);
+    q = cd; q.kh = 5; EXPECT(call(q, dummy, nullptr, dummy, dummy) == DAC_E_ARG);
+    q = cd; q.B = 0; EXPECT(call(q, dummy, nullptr, dummy, dummy) == DAC_E_ARG);
+    q = cd; q.Ws = -3; EXPECT(call(q, dummy, nullptr, dummy, dummy) == DAC_E_ARG);
+    q = cd; q.Cout = 0; EXPECT(call(q, dummy, nullptr, dummy, dummy) == DAC_E_ARG);
+    q = cd; q.Cin = 60; q.K = 60; EXPECT(call(q, dummy, nullptr, dummy, dummy) == DAC_E_ARG);   // not whole vectors
+    q = cd; q.K = 128; EXPECT(call(q, dummy, nullptr, dummy, dummy) == DAC_E_ARG);              // K != kh kw Cin
+    q = cd; q.ldy = 64; EXPECT(call(q, dummy, nullptr, dummy, dummy) == DAC_E_ARG);             // ldy < Cout
+    q = cd; q.act = 7; EXPECT(call(q, dummy, nullptr, dummy, dummy) == DAC_E_ARG);
+    q = cd; q.ksplit = -1; EXPECT(call(q, dummy, nullptr, dummy, dummy) == DAC_E_ARG);
+    q = cd; q.up = 1; EXPECT(call(q, dummy, nullptr, dummy, dummy) == DAC_E_ARG);               // up: 3x3 only
+    q = cd; q.C1 = 32; EXPECT(call(q, dummy, nullptr, dummy, dummy) == DAC_E_ARG);              // C1 < Cin, no x2
+    q = cd; q.C1 = 32; q.ld1 = 32; q.ld2 = 40; EXPECT(call(q, dummy, dummy, dummy, nullptr) == DAC_OK);
+    q = cd; q.ksplit = 2; q.act = 3; EXPECT(call(q, dummy, nullptr, dummy, dummy) == DAC_E_ARG);  // no such kernel
+    q = cd; q.kh = 7; q.C1 = q.Cin = q.ld1 = 8; q.K = 896; q.cwrap = 1; q.dtype = DAC_F32;
+    EXPECT(call(q, dummy, nullptr, dummy, dummy) == DAC_E_ARG);                                  // row-tap dual in fp32
+    q = cd; q.kh = 4; q.Hs = 7; q.K = 16 * 64; EXPECT(call(q, dummy, nullptr, dummy, dummy) == DAC_E_ARG);   // odd input
+  }
   // dac_image_metrics: null pointers and unsupported shapes are refused before any device work.
   unsigned char bytes[4] = {0, 0, 0, 0};
   double rec[8];
