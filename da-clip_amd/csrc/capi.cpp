@@ -53,15 +53,6 @@ bool ignorable(const dac_handle* h, const std::string& k) {
   return false;
 }
 
-float half_to_float(uint16_t x) {
-  const uint32_t s = (x >> 15) & 1, e = (x >> 10) & 0x1f, m = x & 0x3ff;
-  float v;
-  if (e == 0) v = std::ldexp((float)m, -24);
-  else if (e == 31) v = m ? NAN : INFINITY;
-  else v = std::ldexp((float)(m | 0x400), (int)e - 25);
-  return s ? -v : v;
-}
-
 }  // namespace
 
 extern "C" {
@@ -120,13 +111,10 @@ int dac_set_weight(dac_handle* h, const char* key, const void* data, const int64
       std::memcpy(w.v.data(), raw.data(), n * 4);
     } else if (src_dtype == DAC_SRC_BF16) {
       const uint16_t* s = (const uint16_t*)raw.data();
-      for (size_t i = 0; i < n; ++i) {
-        uint32_t u = (uint32_t)s[i] << 16;
-        std::memcpy(&w.v[i], &u, 4);
-      }
+      for (size_t i = 0; i < n; ++i) w.v[i] = dac::bf2f_host(s[i]);
     } else if (src_dtype == DAC_SRC_F16) {
       const uint16_t* s = (const uint16_t*)raw.data();
-      for (size_t i = 0; i < n; ++i) w.v[i] = half_to_float(s[i]);
+      for (size_t i = 0; i < n; ++i) w.v[i] = dac::h2f_host(s[i]);
     } else {
       throw dac::Error(DAC_E_ARG, "unknown src_dtype");
     }
@@ -501,6 +489,209 @@ int dac_op_conv(const dac_conv_desc* d, const void* x1, const void* x2, const vo
   }
   const hipError_t es2 = hipStreamSynchronize(st);
   return e == hipSuccess && es2 == hipSuccess ? DAC_OK : DAC_E_HIP;
+}
+
+namespace {
+
+// What one dac_op_pack call is: the dimensions it uses, its element types and output sizes.
+// False: an argument outside the layout's domain.
+struct PackSpec {
+  dac::Store st = dac::Store::f32;
+  int es = 4, cin = 0, kws = 0;
+  size_t need[3] = {0, 0, 0};
+};
+bool pack_spec(const dac_pack_desc& d, PackSpec& s) {
+  const int LIM = 1 << 16;
+  auto dims = [&](std::initializer_list<int> v) {
+    size_t n = 1;
+    for (int x : v) {
+      if (x < 1 || x > LIM) return false;
+      n *= (size_t)x;
+      if (n > ((size_t)1 << 28)) return false;
+    }
+    return true;
+  };
+  const bool f32 = d.dtype == DAC_F32, h16 = d.dtype == DAC_BF16 || d.dtype == DAC_F16, e4 = d.dtype == DAC_FP8;
+  if (!f32 && !h16 && !e4) return false;
+  if (d.round != 0 && d.round != 1) return false;
+  s.st = d.dtype == DAC_BF16 ? dac::Store::bf16 : d.dtype == DAC_F16 ? dac::Store::f16 : dac::Store::f32;
+  s.es = h16 ? 2 : 4;
+  const size_t es = s.es;
+  switch (d.layout) {
+    case DAC_PACK_CODEC:
+      if (f32 || !dims({d.O})) return false;
+      s.need[0] = (size_t)d.O * (d.flag ? 4 : e4 ? 1 : 2);
+      return true;
+    case DAC_PACK_EMU_FP16:
+      if (!f32 || !dims({d.O})) return false;
+      s.need[0] = (size_t)d.O * 4;
+      return true;
+    case DAC_PACK_CONV:
+    case DAC_PACK_DUAL:
+    case DAC_PACK_UPH_ROW:
+    case DAC_PACK_UPH_COL:
+    case DAC_PACK_Q8C3: {
+      if (!dims({d.O, d.C, d.kh, d.kw}) || d.kwp < 0 || d.kwp > LIM) return false;
+      const int VE = h16 ? 8 : 4;
+      s.cin = (d.C + VE - 1) / VE * VE;
+      s.kws = d.kwp > d.kw ? d.kwp : d.kw;
+      if (!dims({d.O, d.kh, s.kws, s.cin, 2})) return false;
+      const size_t n = (size_t)d.O * d.kh * s.kws * s.cin;
+      if (d.layout == DAC_PACK_CONV) {
+        if (e4) return false;
+        s.need[0] = n * es;
+      } else if (d.layout == DAC_PACK_DUAL) {
+        if (!h16) return false;
+        s.need[0] = 2 * n * 2;
+      } else if (d.layout == DAC_PACK_Q8C3) {
+        if (!e4 || d.O != 64 || d.C != 64 || d.kh != 3 || d.kw != 3 || d.kwp) return false;
+        s.cin = 64;
+        s.need[0] = (size_t)64 * 576;
+        s.need[1] = (size_t)64 * 18;
+      } else {
+        if (e4 || d.kh != 3 || d.kw != 3 || d.kwp) return false;
+        s.need[0] = (size_t)d.O * (d.layout == DAC_PACK_UPH_ROW ? 12 : 16) * s.cin * es;
+      }
+      return true;
+    }
+    case DAC_PACK_GEGLU:
+    case DAC_PACK_GEGLU_GS:
+      if (e4 || !dims({d.F, d.I, 2}) || d.F % (d.layout == DAC_PACK_GEGLU_GS ? 32 : 16)) return false;
+      s.need[0] = (size_t)2 * d.F * d.I * es;
+      s.need[1] = s.need[2] = (size_t)2 * d.F * 4;
+      return true;
+    case DAC_PACK_CONCAT:
+      if (e4 || !dims({d.K, d.O, d.I})) return false;
+      s.need[0] = (size_t)d.K * d.O * d.I * es;
+      return true;
+    case DAC_PACK_TRANSPOSE:
+      if (!f32 || !dims({d.I, d.O})) return false;
+      s.need[0] = (size_t)d.I * d.O * 4;
+      return true;
+    case DAC_PACK_FP8: {
+      if (!e4 || !dims({d.O, d.K}) || !dims({d.O, d.K + 127})) return false;
+      const size_t Kp = (size_t)(d.K + 127) / 128 * 128;
+      s.need[0] = d.O * Kp;
+      s.need[1] = d.O * (Kp / 64);
+      s.need[2] = 4;
+      return true;
+    }
+    case DAC_PACK_FOLD_LN:
+      if (!h16 || !dims({d.O, d.K})) return false;
+      s.need[0] = (size_t)d.O * d.K * 2;
+      s.need[1] = s.need[2] = (size_t)d.O * 4;
+      return true;
+    case DAC_PACK_LA_FOLD:
+      if (e4 || !dims({d.O, d.C}) || d.O % 3) return false;
+      s.need[0] = (size_t)d.O * d.C * es;
+      s.need[1] = 4;
+      return true;
+    default:
+      return false;
+  }
+}
+
+}  // namespace
+
+int dac_op_pack(const dac_pack_desc* d, const float* w, const float* gain, const float* beta, const float* bias,
+                void* const* out, const size_t* cap, size_t* need) {
+  if (!d || !need) return DAC_E_ARG;
+  PackSpec s;
+  if (!pack_spec(*d, s)) return DAC_E_ARG;
+  std::copy(s.need, s.need + 3, need);
+  if (!out) return DAC_OK;                               // size query
+  const bool geglu = d->layout == DAC_PACK_GEGLU || d->layout == DAC_PACK_GEGLU_GS;
+  const bool gained = d->layout == DAC_PACK_FOLD_LN || d->layout == DAC_PACK_LA_FOLD;
+  if (!w || !cap || (geglu && !bias) || (gained && !gain)) return DAC_E_ARG;
+  for (int i = 0; i < 3; ++i)
+    if (s.need[i] && (!out[i] || cap[i] < s.need[i])) return DAC_E_ARG;
+  try {
+    const dac::Round rm = d->round ? dac::Round::keep_sums : dac::Round::rne;
+    auto put = [](void* dst, const auto& v) { std::memcpy(dst, v.data(), v.size() * sizeof(v[0])); };
+    // v [rows][taps][cin] stored in the descriptor's dtype.
+    auto store =[&](void* dst, const std::vector<float>& v, int taps, int cin) {
+      if (s.es == 4) put(dst, v);
+      else put(dst, dac::quantize16(v, taps, cin, s.st, rm));
+    };
+    switch (d->layout) {
+      case DAC_PACK_CODEC:
+        for (int i = 0; i < d->O; ++i) {
+          if (d->dtype == DAC_FP8) {
+            const uint8_t q = dac::f2e4m3_host(w[i]);
+            if (d->flag) ((float*)out[0])[i] = dac::e4m3f_host(q);
+            else ((uint8_t*)out[0])[i] = q;
+          } else {
+            const uint16_t q = dac::enc16(s.st, w[i]);
+            if (d->flag) ((float*)out[0])[i] = dac::dec16(s.st, q);
+            else ((uint16_t*)out[0])[i] = q;
+          }
+        }
+        break;
+      case DAC_PACK_EMU_FP16:
+        put(out[0], dac::emulate16(std::vector<float>(w, w + d->O), 1, d->O, true, rm));
+        break;
+      case DAC_PACK_CONV:
+        store(out[0], dac::pack_ohwi(w, d->O, d->C, d->kh, d->kw, s.kws, s.cin), d->kh * s.kws, s.cin);
+        break;
+      case DAC_PACK_DUAL:
+        put(out[0], dac::pack_dual(w, d->O, d->C, d->kh, d->kw, d->kwp, s.cin, s.st));
+        break;
+      case DAC_PACK_UPH_ROW:
+        store(out[0], dac::fold_row_phase(dac::pack_ohwi(w, d->O, d->C, 3, 3, 3, s.cin), d->O, s.cin), 12, s.cin);
+        break;
+      case DAC_PACK_UPH_COL:
+        store(out[0], dac::fold_rowcol_phase(dac::pack_ohwi(w, d->O, d->C, 3, 3, 3, s.cin), d->O, s.cin), 16, s.cin);
+        break;
+      case DAC_PACK_Q8C3: {
+        const dac::Mx8 m = dac::make_q8c3(dac::pack_ohwi(w, 64, 64, 3, 3, 3, 64));
+        put(out[0], m.w8);
+        put(out[1], m.s8);
+        break;
+      }
+      case DAC_PACK_GEGLU:
+      case DAC_PACK_GEGLU_GS: {
+        const std::vector<int> rows = d->layout == DAC_PACK_GEGLU ? dac::geglu_rows(d->F) : dac::geglu_gs_rows(d->F);
+        store(out[0], dac::gather_rows(w, rows, d->I), 1, d->I);
+        put(out[1], dac::gather_rows(bias, rows, 1));
+        put(out[2], rows);
+        break;
+      }
+      case DAC_PACK_CONCAT: {
+        std::vector<const float*> parts;
+        for (int k = 0; k < d->K; ++k) parts.push_back(w + (size_t)k * d->O * d->I);
+        store(out[0], dac::concat_rows(parts.data(), d->K, d->O, d->I, d->scale), 1, d->I);
+        break;
+      }
+      case DAC_PACK_TRANSPOSE:
+        put(out[0], dac::transpose_io(w, d->I, d->O));
+        break;
+      case DAC_PACK_FP8: {
+        const dac::Mx8 m = dac::make_fp8(std::vector<float>(w, w + (size_t)d->O * d->K), d->O, d->K);
+        put(out[0], m.w8);
+        put(out[1], m.s8);
+        *(int*)out[2] = m.Kp;
+        break;
+      }
+      case DAC_PACK_FOLD_LN: {
+        const dac::FoldedLN f =
+            dac::fold_ln(std::vector<float>(w, w + (size_t)d->O * d->K), d->O, d->K, gain, beta, bias, s.st);
+        put(out[0], f.w);
+        put(out[1], f.cs);
+        put(out[2], f.bias);
+        break;
+      }
+      case DAC_PACK_LA_FOLD: {
+        const dac::LaFold f = dac::fold_la_gain(std::vector<float>(w, w + (size_t)d->O * d->C), d->O, d->C, d->O / 3,
+                                                gain, d->flag != 0);
+        store(out[0], f.wg, 1, d->C);
+        *(float*)out[1] = f.qshift;
+        break;
+      }
+    }
+  } catch (const std::bad_alloc&) {
+    return DAC_E_NOMEM;
+  }
+  return DAC_OK;
 }
 
 size_t dac_image_metrics_workspace(int B, int C, int H, int W, int crop_border) {

@@ -17,15 +17,14 @@ namespace dac {
 
 // ============================================================================= precision probe
 // Debug aid for locating where bf16 storage costs accuracy, fp32 handles only (off by default):
-// DAC_EMU_W / DAC_EMU_A are bit masks of UNet roles whose weights (at packing) / outputs (after
-// each kernel) are rounded to bf16, emulating the bf16 engine one part at a time.
+// DAC_EMU_W (PackKnobs::emu_w) / DAC_EMU_A are bit masks of UNet roles whose weights (at packing)
+// / outputs (after each kernel) are rounded to bf16, emulating the bf16 engine one part at a time.
 enum Role : int { R_INIT = 1, R_RB = 2, R_SAMP = 4, R_LA = 8, R_ST = 16, R_FINAL = 32, R_FIN_RB = 64,
                   R_MID = 128, R_OTHER = 256 };
 static int env_mask(const char* n) {
   const char* v = getenv(n);
   return v ? (int)strtol(v, nullptr, 0) : 0;
 }
-static int emu_w() { static const int m = env_mask("DAC_EMU_W"); return m; }
 // Per-image split-K count for the 3x3 convs (and split-K for the 1x1 GEMMs) of the UNet levels of
 // at most 1024 pixels per image (the 32x32 level at 256^2), set by UNetNet::forward from the
 // handle's policy: Wild-IR (scale-0.5) handles, whose configs[3] slice is 2 images per GPU, use 4;
@@ -83,19 +82,6 @@ static bool no_res_fuse() {
   static const int v = getenv("DAC_NO_RES_FUSE") ? atoi(getenv("DAC_NO_RES_FUSE")) : 0;
   return v != 0;
 }
-// DAC_EMU_WSKIP: comma-separated key substrings whose weights stay fp32 under DAC_EMU_W.
-static bool emu_w_key(const std::string& k) {
-  if (!(emu_w() & key_role(k))) return false;
-  static const std::string skip = getenv("DAC_EMU_WSKIP") ? getenv("DAC_EMU_WSKIP") : "";
-  size_t a = 0;
-  while (a < skip.size()) {
-    size_t b = skip.find(',', a);
-    if (b == std::string::npos) b = skip.size();
-    if (b > a && k.find(skip.substr(a, b - a)) != std::string::npos) return false;
-    a = b + 1;
-  }
-  return true;
-}
 
 // ============================================================================= weights
 const HostW* WStore::get(const std::string& key, std::vector<int64_t> shape) {
@@ -129,269 +115,71 @@ void* DevPool::upload(const void* host, size_t bytes) {
   return p;
 }
 
-uint16_t f2bf_host(float f) {
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-
-static float bf2f_host(uint16_t h) {
-  const uint32_t u = (uint32_t)h << 16;
-  float f;
-  std::memcpy(&f, &u, 4);
-  return f;
-}
-// Host f32 -> IEEE half, round to nearest even (subnormals kept, overflow to +-inf).
-static uint16_t f2h_host(float f) {
-  uint32_t x;
-  std::memcpy(&x, &f, 4);
-  const uint32_t sign = (x >> 16) & 0x8000u, ax = x & 0x7fffffffu;
-  if (ax >= 0x7f800000u) return (uint16_t)(sign | 0x7c00u | (ax > 0x7f800000u ? 0x200u : 0u));
-  if (ax >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);          // >= 65520 -> inf
-  if (ax < 0x38800000u) {                                             // |f| < 2^-14: subnormal
-    float a;
-    std::memcpy(&a, &ax, 4);
-    return (uint16_t)(sign | (uint32_t)std::nearbyint(a * 16777216.f));   // a * 2^24 is exact
-  }
-  uint32_t h = (((ax >> 23) - 112u) << 10) | ((ax & 0x7fffffu) >> 13);
-  const uint32_t rem = ax & 0x1fffu;
-  if (rem > 0x1000u || (rem == 0x1000u && (h & 1u))) ++h;
-  return (uint16_t)(sign | h);
-}
-static float h2f_host(uint16_t h) {
-  const int e = (h >> 10) & 0x1f;
-  const uint32_t m = h & 0x3ffu;
-  float v = e == 0 ? std::ldexp((float)m, -24)
-                   : e == 31 ? (m ? NAN : INFINITY) : std::ldexp((float)(m | 0x400u), e - 25);
-  return (h & 0x8000u) ? -v : v;
-}
-// 16-bit storage codecs of the packed weights (bf16 / IEEE half), round to nearest even.
-struct BF16Codec {
-  static constexpr bool kHalf = false;
-  static uint16_t enc(float f) { return f2bf_host(f); }
-  static float dec(uint16_t h) { return bf2f_host(h); }
-};
-struct F16Codec {
-  static constexpr bool kHalf = true;
-  static uint16_t enc(float f) { return f2h_host(f); }
-  static float dec(uint16_t h) { return h2f_host(h); }
-};
-template <typename T> struct CodecOf { typedef BF16Codec type; };
-template <> struct CodecOf<f16> { typedef F16Codec type; };
-// The 16-bit neighbour of h one step toward f (h != f, both finite); both formats are
-// sign-magnitude, so a magnitude step is +-1 on the bits.
-template <class C>
-static uint16_t step_toward(uint16_t h, float f) {
-  const float v = C::dec(h);
-  const bool up = f > v;
-  if (v == 0.f) return up ? 0x0001 : 0x8001;
-  return (uint16_t)(((v > 0.f) == up) ? h + 1 : h - 1);
-}
-// Weight rounding to 16 bits. bf16 round-to-nearest leaves a per-layer systematic error (the
-// same every step and pixel); by default (DAC_WROUND=1) each bf16 (output row, input channel)
-// group of `taps` kernel taps is rounded so that its sum is kept (greedy flips of the taps
-// closest to the rounding midpoint), which removes the error's response to smooth inputs.
-// fp16 weights keep plain RNE: with an 11-bit significand the flips (up to 1 ulp per tap)
-// cost more texture-response accuracy than the DC error they remove (restoration fixture:
-// dPSNR -1.3e-3 dB with sum-keeping, -1.2e-4 dB with RNE). DAC_WROUND=0: RNE for both,
-// 2: sum-keeping for both.
-static int wround_mode() {
-  static const int m = getenv("DAC_WROUND") ? env_mask("DAC_WROUND") : 1;   // default: sum-keeping
-  return m;
-}
-// DAC_WROUND_KEY=<substring>: sum-keeping rounding for the conv weights whose state-dict key
-// contains it, whatever DAC_WROUND says for the rest (a per-layer precision probe).
-static bool wround_key(const std::string& key) {
-  static const char* k = getenv("DAC_WROUND_KEY");
-  return k && *k && !key.empty() && key.find(k) != std::string::npos;
-}
-template <class C>
-static std::vector<uint16_t> quantize16(const std::vector<float>& v, int taps, int cin, bool keep_sums = false) {
-  std::vector<uint16_t> h(v.size());
-  for (size_t i = 0; i < v.size(); ++i) h[i] = C::enc(v[i]);
-  const int m = keep_sums ? 2 : wround_mode();
-  if (taps < 2 || m == 0 || (m == 1 && C::kHalf)) return h;
-  const size_t rows = v.size() / ((size_t)taps * cin);
-  std::vector<size_t> idx(taps);
-  std::vector<char> used(taps);
-  for (size_t o = 0; o < rows; ++o)
-    for (int c = 0; c < cin; ++c) {
-      double r = 0;
-      for (int t = 0; t < taps; ++t) {
-        idx[t] = (o * taps + t) * cin + c;
-        used[t] = 0;
-        r += (double)v[idx[t]] - C::dec(h[idx[t]]);
-      }
-      for (int it = 0; it < taps; ++it) {
-        int best = -1;
-        double br = std::fabs(r);
-        for (int t = 0; t < taps; ++t) {
-          const float w = v[idx[t]];
-          const uint16_t q = h[idx[t]];
-          if (used[t] || C::dec(q) == w || !std::isfinite(w)) continue;
-          const double nr = r + (double)C::dec(q) - C::dec(step_toward<C>(q, w));
-          if (std::fabs(nr) < br) { br = std::fabs(nr); best = t; }
-        }
-        if (best < 0) break;
-        const uint16_t q = h[idx[best]], q2 = step_toward<C>(q, v[idx[best]]);
-        r += (double)C::dec(q) - C::dec(q2);
-        h[idx[best]] = q2;
-        used[best] = 1;
-      }
-    }
-  return h;
-}
-
-// Host f32 -> OCP e4m3 (e4m3fn: bias 7, max 448, no infinities), round to nearest even,
-// saturating to +-448.
-static uint8_t f2e4m3_host(float f) {
-  const uint8_t sign = std::signbit(f) ? 0x80 : 0;
-  const float a = std::fabs(f);
-  if (std::isnan(a)) return 0x7f;
-  if (a >= 464.f) return sign | 0x7e;
-  if (a < std::ldexp(1.f, -6)) {                       // subnormal: q * 2^-9
-    const int q = (int)std::nearbyint(a * 512.f);
-    return sign | (uint8_t)(q >= 8 ? 0x08 : q);
-  }
-  int e;
-  std::frexp(a, &e);                                   // a = m * 2^e, m in [0.5, 1)
-  int E = e - 1 + 7;
-  int q = (int)std::nearbyint((a / std::ldexp(1.f, e - 1) - 1.f) * 8.f);
-  if (q == 8) { q = 0; ++E; }
-  if (E > 15 || (E == 15 && q == 7)) return sign | 0x7e;
-  return sign | (uint8_t)(E << 3) | (uint8_t)q;
-}
-
+// Packs a handle's weights: WStore lookups (strict-load bookkeeping), which forms a layer gets
+// (ConvW fields) and the uploads. Every value comes from pack.h; no arithmetic on weights here.
 template <typename T>
 struct Packer {
   DevPool& pool;
   WStore& ws;
+  const PackKnobs kn;                  // the environment's packing switches, read once per handle
   bool fp8 = false;                    // also build the e4m3 weights of every eligible layer
   bool q8 = false;                     // fp8 handles' UNet: e4m3 64 -> 64 ResBlock block2 weights
   static constexpr int VE = sizeof(T) == 2 ? 8 : 4;
+  static constexpr Store ST = sizeof(T) == 4 ? Store::f32 : std::is_same<T, f16>::value ? Store::f16 : Store::bf16;
 
-  // Row-phase weights of a 3x3 conv applied after a 2x nearest upsample (ConvArgs::uph): output
-  // row 2i reads source rows (i-1 | i, i) and row 2i+1 (i, i | i+1), so the kernel rows fold to
-  // (W0, W1+W2) and (W0+W1, W2), summed in fp32 and rounded to T once.
+  template <class X> const X* up(const std::vector<X>& v) { return (const X*)pool.upload(v.data(), v.size() * sizeof(X)); }
+  // fp32 handles: is `key` a weight the DAC_EMU_W probe rounds as a 16-bit handle would.
+  bool emu_key(const std::string& key) const { return (kn.emu_w & key_role(key)) && !kn.emu_skips(key); }
+
+  // Row-phase weights of a 3x3 conv applied after a 2x nearest upsample (ConvArgs::uph), rounded
+  // to T once: 16-bit 3x3 without a padded kernel row.
   void make_uph(ConvW& cw, const std::vector<float>& p, const std::string& key) {
     if (sizeof(T) != 2 || cw.kh != 3 || cw.kw != 3 || cw.kwp || p.size() != (size_t)cw.cout * 9 * cw.cin) return;
-    if (getenv("DAC_UPH") && atoi(getenv("DAC_UPH")) == 0) return;
-    const size_t R = (size_t)3 * cw.cin;                 // one kernel row [3][cin]
-    std::vector<float> q((size_t)cw.cout * 4 * R);
-    for (int o = 0; o < cw.cout; ++o) {
-      const float* w = &p[(size_t)o * 3 * R];
-      float* d = &q[(size_t)o * 4 * R];
-      for (size_t k = 0; k < R; ++k) {
-        d[k] = w[k];
-        d[R + k] = w[R + k] + w[2 * R + k];
-        d[2 * R + k] = w[k] + w[R + k];
-        d[3 * R + k] = w[2 * R + k];
-      }
-    }
-    cw.wph = upload_T(q, key, 12, cw.cin);
-    // Columns fold the same way: set (b, t) of row set r = sum of the kernel taps (kh, kw) with
-    // kh in rows(r), kw in cols(b, t); rows / cols: (0 | 1,2) for parity 0, (0,1 | 2) for 1.
-    // Opt-in (DAC_UPH=2): measured +0.1-0.4 % in the network over the row form (upsample convs
-    // 62 -> 54 and 53 -> 44 us at 256^2 / 128^2), with the restoration fixture's fp16 dPSNR at
-    // -8.3e-4 dB against -2.4e-4 for the row form (RMS error unchanged, 2.2e-4): too close to
-    // the 1e-3 dB bar for the default.
-    if (!getenv("DAC_UPH") || atoi(getenv("DAC_UPH")) != 2) return;
-    static const int lo[4] = {0, 1, 0, 2}, hi[4] = {0, 2, 1, 2};   // index ranges of the 4 sets
-    const size_t C = cw.cin;
-    std::vector<float> q2((size_t)cw.cout * 16 * C);
-    for (int o = 0; o < cw.cout; ++o)
-      for (int rs = 0; rs < 4; ++rs)
-        for (int cs = 0; cs < 4; ++cs)
-          for (size_t c = 0; c < C; ++c) {
-            float v = 0.f;
-            for (int kh = lo[rs]; kh <= hi[rs]; ++kh)
-              for (int kw = lo[cs]; kw <= hi[cs]; ++kw) v += p[(((size_t)o * 3 + kh) * 3 + kw) * C + c];
-            q2[(((size_t)o * 4 + rs) * 4 + cs) * C + c] = v;
-          }
-    cw.wpc = upload_T(q2, key, 16, cw.cin);
+    if (kn.uph == 0) return;
+    cw.wph = upload_T(fold_row_phase(p, cw.cout, cw.cin), key, 12, cw.cin);
+    // The row- and column-phase form is opt-in (DAC_UPH=2): measured +0.1-0.4 % in the network over
+    // the row form (upsample convs 62 -> 54 and 53 -> 44 us at 256^2 / 128^2), with the restoration
+    // fixture's fp16 dPSNR at -8.3e-4 dB against -2.4e-4 for the row form (RMS error unchanged,
+    // 2.2e-4): too close to the 1e-3 dB bar for the default.
+    if (kn.uph == 2) cw.wpc = upload_T(fold_rowcol_phase(p, cw.cout, cw.cin), key, 16, cw.cin);
   }
 
-  // conv3q weights of a 3x3 64 -> 64 conv from its packed [64][3][3][64] fp32 values: e4m3 bytes
-  // [64][9][64] with one E8M0 exponent per (output channel, tap, 32-channel half), the smallest
-  // with max |w| / 2^e <= 448.
+  // conv3q weights of a 3x3 64 -> 64 conv from its packed [64][3][3][64] fp32 values.
   void make_q8c3(ConvW& cw, const std::vector<float>& p) {
     if (!q8 || sizeof(T) != 2 || cw.kh != 3 || cw.kw != 3 || cw.cin != 64 || cw.cout != 64 || cw.kwp ||
         p.size() != (size_t)64 * 576)
       return;
-    std::vector<uint8_t> w8((size_t)64 * 576), s8((size_t)64 * 18);
-    for (int n = 0; n < 64; ++n)
-      for (int t = 0; t < 9; ++t)
-        for (int h = 0; h < 2; ++h) {
-          const float* src = &p[(size_t)n * 576 + t * 64 + 32 * h];
-          float mx = 0.f;
-          for (int c = 0; c < 32; ++c) mx = std::max(mx, std::fabs(src[c]));
-          int e = mx > 0.f ? (int)std::ceil(std::log2((double)mx / 448.0)) : 0;
-          e = std::min(126, std::max(-126, e));
-          s8[(size_t)n * 18 + t * 2 + h] = (uint8_t)(127 + e);
-          for (int c = 0; c < 32; ++c) w8[(size_t)n * 576 + t * 64 + 32 * h + c] = f2e4m3_host(std::ldexp(src[c], -e));
-        }
-    cw.q8w = (const uint8_t*)pool.upload(w8.data(), w8.size());
-    cw.q8s = (const uint8_t*)pool.upload(s8.data(), s8.size());
+    const Mx8 m = dac::make_q8c3(p);
+    cw.q8w = up(m.w8);
+    cw.q8s = up(m.s8);
   }
 
-  // fp8 copy of a packed [O][K] weight (conv8.hip): K padded to a multiple of 128 with zeros,
-  // one E8M0 exponent per (row, 64-k block) chosen so the block's largest |w| / 2^e <= 448.
+  // fp8 copy of a packed [O][K] weight (conv8.hip).
   void make_fp8(ConvW& cw, const std::vector<float>& p, int O, int K) {
     if (!fp8 || sizeof(T) != 2 || cw.cin % 64) return;
-    const int Kp = (K + 127) / 128 * 128;
-    std::vector<uint8_t> w8((size_t)O * Kp, 0), s8((size_t)O * (Kp / 64), 127);
-    for (int o = 0; o < O; ++o)
-      for (int b = 0; b < Kp / 64; ++b) {
-        float mx = 0.f;
-        for (int k = 64 * b; k < std::min(64 * b + 64, K); ++k) mx = std::max(mx, std::fabs(p[(size_t)o * K + k]));
-        int e = mx > 0.f ? (int)std::ceil(std::log2(mx / 448.f)) : 0;
-        e = std::min(126, std::max(-126, e));
-        s8[(size_t)o * (Kp / 64) + b] = (uint8_t)(127 + e);
-        const float inv = std::ldexp(1.f, -e);
-        for (int k = 64 * b; k < std::min(64 * b + 64, K); ++k)
-          w8[(size_t)o * Kp + k] = f2e4m3_host(p[(size_t)o * K + k] * inv);
-      }
-    cw.w8 = (const uint8_t*)pool.upload(w8.data(), w8.size());
-    cw.ws8 = (const uint8_t*)pool.upload(s8.data(), s8.size());
-    cw.kp8 = Kp;
+    const Mx8 m = dac::make_fp8(p, O, K);
+    cw.w8 = up(m.w8);
+    cw.ws8 = up(m.s8);
+    cw.kp8 = m.Kp;
   }
 
-  // v: packed [rows][taps][cin] weights.
+  // v: packed [rows][taps][cin] weights, stored in T.
   const void* upload_T(const std::vector<float>& v, const std::string& key = "", int taps = 1, int cin = 1) {
     if (cin <= 1) cin = (int)v.size(), taps = 1;
-    if (sizeof(T) == 4) {
-      if (!emu_w_key(key)) return pool.upload(v.data(), v.size() * 4);
-      std::vector<float> q(v.size());
-      if (getenv("DAC_EMU_FP16") && atoi(getenv("DAC_EMU_FP16"))) {
-        for (size_t i = 0; i < v.size(); ++i) {        // round to 11 significant bits (normals)
-          int e;
-          const double m = std::frexp((double)v[i], &e);
-          q[i] = (float)std::ldexp(std::nearbyint(std::ldexp(m, 11)), e - 11);
-        }
-        return pool.upload(q.data(), q.size() * 4);
-      }
-      const std::vector<uint16_t> h = quantize16<BF16Codec>(v, taps, cin);
-      for (size_t i = 0; i < v.size(); ++i) q[i] = bf2f_host(h[i]);
-      return pool.upload(q.data(), q.size() * 4);
+    if (ST == Store::f32) {
+      if (!emu_key(key)) return up(v);
+      return up(emulate16(v, taps, cin, kn.emu_fp16, kn.round(Store::bf16, "")));
     }
-    const std::vector<uint16_t> h = quantize16<typename CodecOf<T>::type>(v, taps, cin, wround_key(key));
-    return pool.upload(h.data(), h.size() * 2);
+    return up(quantize16(v, taps, cin, ST, kn.round(ST, key)));
   }
   const float* f32(const std::string& key, std::vector<int64_t> shape) {
     const HostW* w = ws.get(key, shape);
-    if (!w) return nullptr;
-    return (const float*)pool.upload(w->v.data(), w->v.size() * 4);
+    return w ? up(w->v) : nullptr;
   }
   // [I][O] -> [O][I] fp32 (for `pooled @ proj`).
   const float* f32_t(const std::string& key, int I, int O) {
     const HostW* w = ws.get(key, {I, O});
-    if (!w) return nullptr;
-    std::vector<float> t((size_t)I * O);
-    for (int i = 0; i < I; ++i)
-      for (int o = 0; o < O; ++o) t[(size_t)o * I + i] = w->v[(size_t)i * O + o];
-    return (const float*)pool.upload(t.data(), t.size() * 4);
+    return w ? up(transpose_io(w->v.data(), I, O)) : nullptr;
   }
   static int pad_to(int c, int v) { return (c + v - 1) / v * v; }
   // conv weight [O][C][kh][kw] (4-D key) or linear [O][C] (2-D key, kh = kw = 1).
@@ -406,12 +194,7 @@ struct Packer {
     const HostW* w = linear2d ? ws.get(key, {O, C}) : ws.get(key, {O, C, kh, kw});
     if (!bkey.empty()) cw.b = f32(bkey, {O});
     if (!w) return cw;
-    std::vector<float> p((size_t)O * kh * kws * cw.cin, 0.f);
-    for (int o = 0; o < O; ++o)
-      for (int c = 0; c < C; ++c)
-        for (int y = 0; y < kh; ++y)
-          for (int x = 0; x < kw; ++x)
-            p[(((size_t)o * kh + y) * kws + x) * cw.cin + c] = w->v[(((size_t)o * C + c) * kh + y) * kw + x];
+    std::vector<float> p = pack_ohwi(w->v.data(), O, C, kh, kw, kws, cw.cin);
     cw.w = upload_T(p, key, kh * kws, cw.cin);
     make_fp8(cw, p, O, kh * kws * cw.cin);
     if (keep) *keep = std::move(p);
@@ -420,10 +203,9 @@ struct Packer {
   ConvW linear(const std::string& key, int O, int I, const std::string& bkey = "") {
     return conv(key, O, I, 1, 1, bkey, true);
   }
-  // Split-precision weights (16-bit handles; fp32 handles keep plain fp32 weights): hi = RNE(w),
-  // lo = RNE(w - hi), packed [O][kh][kws][hi cin | lo cin], or, for the 7x7 row-tap layout
-  // (kwp > kw), [O][hi rows | lo rows]. The layer then computes A.hi + A.lo in one fp32
-  // accumulator: weight error ~2^-17 (bf16) / 2^-23 (f16) relative instead of 2^-9 / 2^-12.
+  // Split-precision weights (16-bit handles; fp32 handles keep plain fp32 weights), pack_dual's
+  // [hi | lo] layouts. The layer then computes A.hi + A.lo in one fp32 accumulator: weight error
+  // ~2^-17 (bf16) / 2^-23 (f16) relative instead of 2^-9 / 2^-12.
   ConvW conv_dual(const std::string& key, int O, int C, int kh, int kw, const std::string& bkey = "",
                   int kwp = 0) {
     if (sizeof(T) == 4) return conv(key, O, C, kh, kw, bkey, false, kwp);
@@ -431,34 +213,13 @@ struct Packer {
     cw.cout = O; cw.cin_real = C; cw.cin = pad_to(C, VE); cw.kh = kh; cw.kw = kw;
     cw.kwp = kwp > kw ? kwp : 0;
     cw.dual = 1;
-    const int kws = cw.kwp ? cw.kwp : kw;
     const HostW* w = ws.get(key, {O, C, kh, kw});
     if (!bkey.empty()) cw.b = f32(bkey, {O});
     if (!w) return cw;
-    const size_t per = (size_t)kh * kws * cw.cin;                // one precision part of a row
-    std::vector<uint16_t> h((size_t)O * 2 * per, 0);
-    for (int o = 0; o < O; ++o)
-      for (int c = 0; c < C; ++c)
-        for (int y = 0; y < kh; ++y)
-          for (int x = 0; x < kw; ++x) {
-            const float v = w->v[(((size_t)o * C + c) * kh + y) * kw + x];
-            using C = typename CodecOf<T>::type;
-            const uint16_t hi = C::enc(v), lo = C::enc(v - C::dec(hi));
-            const size_t tap = (size_t)y * kws + x;
-            if (cw.kwp) {
-              h[(size_t)o * 2 * per + tap * cw.cin + c] = hi;
-              h[(size_t)o * 2 * per + per + tap * cw.cin + c] = lo;
-            } else {
-              h[(size_t)o * 2 * per + tap * 2 * cw.cin + c] = hi;
-              h[(size_t)o * 2 * per + tap * 2 * cw.cin + cw.cin + c] = lo;
-            }
-          }
-    cw.w = pool.upload(h.data(), h.size() * 2);
+    cw.w = up(pack_dual(w->v.data(), O, C, kh, kw, cw.kwp, cw.cin, ST));
     return cw;
   }
-  // Input-LayerNorm fold of a packed [O][K] 1x1 weight p (ConvArgs::lnf_cs; 16-bit handles):
-  // w = p diag(g) stored in T, cs[n] = sum_k w[n][k] over the STORED (rounded) values, bias
-  // = pb + p beta. LN(x) p^T + pb = rstd (x w^T - mean cs) + bias.
+  // Input-LayerNorm fold of a packed [O][K] 1x1 weight p (ConvArgs::lnf_cs; 16-bit handles only).
   struct Folded { ConvW cw; const float* cs = nullptr; };
   // bkey empty: a gain-only LayerNorm (module_util.py:77-86); gshape: the gain's stored shape.
   Folded fold_ln(const ConvW& base, const std::vector<float>& p, int O, int K, const std::string& gkey,
@@ -471,84 +232,46 @@ struct Packer {
     const HostW* g = ws.get(gkey, gshape);
     const HostW* be = bkey.empty() ? nullptr : ws.get(bkey, {K});
     if (!g || (!bkey.empty() && !be) || p.size() != (size_t)O * K || base.cin != K) return f;
-    std::vector<float> w(p.size()), cs(O), bias(O);
-    for (int o = 0; o < O; ++o)
-      for (int k = 0; k < K; ++k) w[(size_t)o * K + k] = p[(size_t)o * K + k] * g->v[k];
-    using C = typename CodecOf<T>::type;
-    const std::vector<uint16_t> h = quantize16<C>(w, 1, K);
-    for (int o = 0; o < O; ++o) {
-      double c = 0, b = pb ? (*pb)[o] : 0.0;
-      for (int k = 0; k < K; ++k) {
-        c += C::dec(h[(size_t)o * K + k]);
-        if (be) b += (double)p[(size_t)o * K + k] * be->v[k];
-      }
-      cs[o] = (float)c;
-      bias[o] = (float)b;
-    }
-    f.cw.w = pool.upload(h.data(), h.size() * 2);
-    f.cw.b = (const float*)pool.upload(bias.data(), bias.size() * 4);
-    f.cs = (const float*)pool.upload(cs.data(), cs.size() * 4);
+    const FoldedLN fl = dac::fold_ln(p, O, K, g->v.data(), be ? be->v.data() : nullptr, pb ? pb->data() : nullptr, ST);
+    f.cw.w = up(fl.w);
+    f.cw.b = up(fl.bias);
+    f.cs = up(fl.cs);
     return f;
   }
-  // Row-concatenation of several [Oi][I] linears (q | k | v) into one GEMM.
-  // The first block's rows are multiplied by `scale0` before rounding (q prescaled for the
-  // attention kernel's log2-domain softmax).
+  // Row-concatenation of several [Oi][I] linears (q | k | v) into one GEMM, the first block's
+  // rows times `scale0` before rounding.
   ConvW concat(const std::vector<std::string>& keys, int O, int I, std::vector<float>* keep = nullptr,
                float scale0 = 1.f) {
     ConvW cw;
     cw.cout = O * (int)keys.size(); cw.cin = cw.cin_real = I;
-    std::vector<float> p;
-    bool ok = true;
-    for (auto& k : keys) {
-      const HostW* w = ws.get(k, {O, I});
-      if (!w) { ok = false; continue; }
-      p.insert(p.end(), w->v.begin(), w->v.end());
-    }
-    if (ok && scale0 != 1.f)
-      for (size_t i = 0; i < (size_t)O * I; ++i) p[i] *= scale0;
-    if (ok) {
-      cw.w = upload_T(p, keys[0]);
-      make_fp8(cw, p, cw.cout, I);
-      if (keep) *keep = std::move(p);
-    }
+    std::vector<const float*> parts;
+    for (auto& k : keys)
+      if (const HostW* w = ws.get(k, {O, I})) parts.push_back(w->v.data());
+    if (parts.size() != keys.size()) return cw;
+    std::vector<float> p = concat_rows(parts.data(), (int)parts.size(), O, I, scale0);
+    cw.w = upload_T(p, keys[0]);
+    make_fp8(cw, p, cw.cout, I);
+    if (keep) *keep = std::move(p);
     return cw;
   }
-  // GEGLU proj [2F][I] (+bias): rows reordered so each 32-row group holds 16 "x" rows then
-  // their 16 "gate" rows; the conv epilogue pairs accumulator tiles j, j+1.
-  ConvW geglu(const std::string& key, const std::string& bkey, int F, int I, std::vector<float>* keep = nullptr,
-              std::vector<float>* keep_b = nullptr) {
+  // GEGLU proj [2F][I] (+bias) in the geglu_rows order and, for 16-bit handles with F % 32 == 0,
+  // again in the swapped-tile order (ConvArgs::w_gs).
+  ConvW geglu(const std::string& key, const std::string& bkey, int F, int I) {
     ConvW cw;
     cw.cout = 2 * F; cw.cin = cw.cin_real = I;
     const HostW* w = ws.get(key, {2 * F, I});
     const HostW* b = ws.get(bkey, {2 * F});
     if (!w || !b) return cw;
-    std::vector<float> p((size_t)2 * F * I), pb(2 * F);
-    for (int r = 0; r < 2 * F; ++r) {
-      const int g = r / 32, s = r % 32;
-      const int src = s < 16 ? 16 * g + s : F + 16 * g + (s - 16);
-      std::copy(w->v.begin() + (size_t)src * I, w->v.begin() + (size_t)(src + 1) * I,
-                p.begin() + (size_t)r * I);
-      pb[r] = b->v[src];
-    }
+    const std::vector<int> rows = geglu_rows(F);
+    const std::vector<float> p = gather_rows(w->v.data(), rows, I);
     cw.w = upload_T(p, key);
     make_fp8(cw, p, 2 * F, I);
-    cw.b = (const float*)pool.upload(pb.data(), pb.size() * 4);
+    cw.b = up(gather_rows(b->v.data(), rows, 1));
     if (sizeof(T) == 2 && F % 32 == 0) {
-      // Swapped-tile order (ConvArgs::w_gs): row L of 64-row group G = L / 64, lane group
-      // lg = (L % 64) / 16, e = L % 16 is x (e < 8) or gate (e >= 8) of output channel
-      // 32 G + 8 lg + (e & 7).
-      std::vector<float> q((size_t)2 * F * I), qb(2 * F);
-      for (int L = 0; L < 2 * F; ++L) {
-        const int G = L / 64, lg = (L % 64) / 16, e = L % 16;
-        const int src = (e < 8 ? 0 : F) + 32 * G + 8 * lg + (e & 7);
-        std::copy(w->v.begin() + (size_t)src * I, w->v.begin() + (size_t)(src + 1) * I, q.begin() + (size_t)L * I);
-        qb[L] = b->v[src];
-      }
-      cw.w_gs = upload_T(q, key);
-      cw.b_gs = (const float*)pool.upload(qb.data(), qb.size() * 4);
+      const std::vector<int> gs = geglu_gs_rows(F);
+      cw.w_gs = upload_T(gather_rows(w->v.data(), gs, I), key);
+      cw.b_gs = up(gather_rows(b->v.data(), gs, 1));
     }
-    if (keep) *keep = std::move(p);
-    if (keep_b) *keep_b = std::move(pb);
     return cw;
   }
 };
@@ -908,23 +631,11 @@ struct UNetNet {
         if (fq.cs) { a.la.qkv_f = fq.cw; a.la.qkv_cs = fq.cs; }
       }
       if (const HostW* g = P.ws.get(p + "fn.norm.g", {1, C, 1, 1}); g && pq.size() == (size_t)384 * C) {
-        // The fused kernels take the PreNorm gain inside to_qkv. |q_j| = |(Wq_j . g) . LN(x)| <=
-        // ||Wq_j . g|| sqrt(C) (||LN(x)|| <= sqrt(C)): with margin for the 16-bit operands, the
-        // largest over the 128 q rows is la_apply's softmax shift when <= 40 (e^-80 is normal).
-        std::vector<float> wg(pq.size());
-        double mx = 0;
-        for (int o = 0; o < 384; ++o) {
-          double n2 = 0;
-          for (int k = 0; k < C; ++k) {
-            wg[(size_t)o * C + k] = pq[(size_t)o * C + k] * g->v[k];
-            n2 += (double)wg[(size_t)o * C + k] * wg[(size_t)o * C + k];
-          }
-          if (o < 128) mx = std::max(mx, std::sqrt(n2));
-        }
-        a.la.wqkv_g = P.upload_T(wg, f + "to_qkv.weight", 1, C);
-        const double bound = 1.01 * mx * std::sqrt((double)C) + 0.05;
-        static const bool qs_on = !getenv("DAC_LA_QSHIFT") || atoi(getenv("DAC_LA_QSHIFT")) != 0;
-        a.la.qshift = (qs_on && bound <= 40.0) ? (float)bound : 0.f;
+        // The fused kernels take the PreNorm gain inside to_qkv, and la_apply its softmax shift
+        // from the bound on the 128 q rows (fold_la_gain).
+        const LaFold lf = fold_la_gain(pq, 384, C, 128, g->v.data(), P.kn.la_qshift);
+        a.la.wqkv_g = P.upload_T(lf.wg, f + "to_qkv.weight", 1, C);
+        a.la.qshift = lf.qshift;
       }
       a.la.wout = P.f32(f + "to_out.0.weight", {C, 128, 1, 1});
       a.la.bout = P.f32(f + "to_out.0.bias", {C});
@@ -1681,15 +1392,12 @@ struct VitNet {
   }
   Tower load_tower(Packer<T>& Pk, const std::string& p, bool control) {
     Tower t;
-    std::vector<float> pk;
-    t.conv1 = Pk.conv(p + "conv1.weight", D, 3, P, P, "", false, 0, &pk);
-    const int K = 3 * P * P, cp = t.conv1.cin;
-    if (K % 64 == 0 && !pk.empty() && !(getenv("DAC_VIT_GEMM") && atoi(getenv("DAC_VIT_GEMM")) == 0)) {
-      // [D][P][P][cin_pad] -> [D][P][P][3]: the same weights, the padding channels dropped.
-      std::vector<float> q((size_t)D * K);
-      for (size_t o = 0; o < (size_t)D; ++o)
-        for (int t2 = 0; t2 < P * P; ++t2)
-          for (int c = 0; c < 3; ++c) q[(o * P * P + t2) * 3 + c] = pk[(o * P * P + t2) * cp + c];
+    t.conv1 = Pk.conv(p + "conv1.weight", D, 3, P, P);
+    const int K = 3 * P * P;
+    const HostW* w1 = t.conv1.w ? Pk.ws.get(p + "conv1.weight", {D, 3, P, P}) : nullptr;
+    if (K % 64 == 0 && w1 && !(getenv("DAC_VIT_GEMM") && atoi(getenv("DAC_VIT_GEMM")) == 0)) {
+      // [D][P][P][3]: the same weights without the padding channels, as one GEMM operand.
+      const std::vector<float> q = pack_ohwi(w1->v.data(), D, 3, P, P, P, 3);
       ConvW& g = t.conv1g;
       g.cout = D; g.cin = g.cin_real = K; g.kh = g.kw = 1;
       g.w = Pk.upload_T(q, p + "conv1.weight", P * P, 3);
@@ -1854,7 +1562,7 @@ class EngineT : public Engine {
 
   void finalize(WStore& ws) override {
     HIP_OK(hipSetDevice(dev));
-    Packer<T> P{pool, ws};
+    Packer<T> P{pool, ws, pack_knobs_from_env()};
     // fp8 handles: the UNet runs the 16-bit kernels with its 64 -> 64 ResBlock block2 convs on
     // e4m3 (q8: conv3q.hip, fed by e4m3 block1 epilogues); the ViT's GEMMs take e4m3 MX weights
     // (conv8.hip). (conv8 on the UNet's layers measured 1.2-3.5x slower than their 16-bit

@@ -1,5 +1,5 @@
-// engine.h — host-side runtime of libdaclip_hip: weight store + repacking, workspace arena,
-// and the network executors (ConditionalUNet, DaCLIP vision towers, IR-SDE loop).
+// engine.h — host-side runtime of libdaclip_hip: weight store (packing itself is pack.h),
+// workspace arena, and the network executors (ConditionalUNet, DaCLIP vision towers, IR-SDE loop).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -14,6 +14,7 @@
 #include "../../include/daclip_hip.h"
 #include "common.h"
 #include "kernels.h"
+#include "pack.h"
 
 namespace dac {
 
@@ -51,8 +52,6 @@ struct DevPool {
   void* alloc(size_t bytes);
   void* upload(const void* host, size_t bytes);
 };
-
-uint16_t f2bf_host(float f);
 
 // Packed conv/linear weight: [cout][kh][kw][cin] in the compute dtype (+ fp32 bias).
 struct ConvW {

@@ -267,7 +267,7 @@ int dac_op_linear_attention_weff(const void* qkv, const float* wout, void* weff,
  * +res2 -> +bbias. kh in {1, 3, 4, 7} fixes the window: 1x1 s1 p0, 3x3 s1 p1, 4x4 s2 p1, 7x7 s1 p3.
  * x1, x2, w, res1, res2, w_gs, y are in `dtype` (DAC_F32 / DAC_BF16 / DAC_F16); bias [Cout],
  * ss (scale [b*ss_ld + n], shift [b*ss_ld + Cout + n]), bbias [b*bb_ld + n] and b_gs are fp32.
- * w is [Cout][K] in the packed layout the kernels read (engine.cpp Packer): K = kh*kw*Cin, the
+ * w is [Cout][K] in the packed layout the kernels read (csrc/pack.h): K = kh*kw*Cin, the
  * 7x7 row-tap layout with kw padded to 8 (K = 7*8*Cin, twice that with cwrap = 1 for [hi rows |
  * lo rows]), or [hi Cin | lo Cin] per tap over an input read twice (x2 = x1, or cwrap = Cin / 2).
  * act: 0 none, 1 SiLU, 2 GELU, 3 GEGLU (w in the 16-row interleaved order, y has Cout / 2
@@ -299,6 +299,44 @@ enum { DAC_CONV_KEEP = -1000, DAC_CONV_PLAN_N = 8 };
 int dac_op_conv(const dac_conv_desc* d, const void* x1, const void* x2, const void* w, const float* bias,
                 const float* ss, const void* res1, const void* res2, const float* bbias, const void* w_gs,
                 const float* b_gs, void* y, int* plan_out, void* stream);
+
+/* Host-only test hook: one weight-packing function of csrc/pack.h, the code dac_finalize_weights
+ * packs with, on host arrays. No HIP call, so it works without a GPU. w (and gain / beta / bias
+ * where the layout has them) are fp32 as a checkpoint stores them; `dtype` is the storage type
+ * (DAC_BF16 / DAC_F16: uint16 bits; DAC_F32: the fp32 values before rounding; DAC_FP8 for the e4m3
+ * layouts), `round` 0 = nearest even, 1 = the sum-keeping rounding over each (row, channel) group
+ * of taps. need[3] always receives the outputs' byte sizes; out == NULL is the size query, else
+ * out[i] / cap[i] are the buffers and their capacities for every need[i] > 0. Layouts (outputs):
+ *   CODEC      w[O] -> bf16 / f16 / e4m3 element-wise; flag = 1: the codes decoded again (fp32)
+ *   EMU_FP16   w[O] -> fp32 rounded to 11 significant bits (DAC_F32)
+ *   CONV       w[O][C][kh][kw] -> [O][kh][kws][cin], cin = C up to 8 (16-bit) / 4, kws = max(kw, kwp)
+ *   DUAL       ... -> split precision [O][kh][kw][hi cin | lo cin], kwp > kw: [O][hi rows | lo rows]
+ *   UPH_ROW / UPH_COL   3x3 -> the row-phase [O][4][3][cin] / row+column-phase [O][4][4][cin] folds
+ *   Q8C3       64x64x3x3 -> e4m3 [64][9][64], E8M0 [64][9][2]
+ *   GEGLU / GEGLU_GS    w[2F][I], bias[2F] -> rows gathered (GS: F % 32 == 0, else F % 16 == 0);
+ *              gathered bias (fp32); the source row of each packed row (int32)
+ *   CONCAT     w[K][O][I] -> [K*O][I], the first block times `scale`
+ *   TRANSPOSE  w[I][O] -> [O][I] (DAC_F32)
+ *   FP8        w[O][K] -> e4m3 [O][Kp]; E8M0 [O][Kp/64]; Kp (int32), K up to a multiple of 128
+ *   FOLD_LN    w[O][K], gain[K], beta[K] or NULL, bias[O] or NULL -> w' (16-bit); cs[O]; bias'[O]
+ *   LA_FOLD    w[O][C] (first O/3 rows = q), gain[C] -> w diag(gain); qshift (fp32, 0 with flag = 0)
+ * DAC_E_ARG before any buffer is touched: a null descriptor, need, w, required gain / bias, or
+ * output; an unknown layout, dtype (or one the layout does not store) or round; a non-positive
+ * dimension; a layout's precondition above; a capacity below the needed size. */
+enum dac_pack_layout {
+  DAC_PACK_CODEC = 0, DAC_PACK_EMU_FP16, DAC_PACK_CONV, DAC_PACK_DUAL, DAC_PACK_UPH_ROW, DAC_PACK_UPH_COL,
+  DAC_PACK_Q8C3, DAC_PACK_GEGLU, DAC_PACK_GEGLU_GS, DAC_PACK_CONCAT, DAC_PACK_TRANSPOSE, DAC_PACK_FP8,
+  DAC_PACK_FOLD_LN, DAC_PACK_LA_FOLD
+};
+typedef struct dac_pack_desc {
+  int layout, dtype, round;
+  int O, C, kh, kw, kwp;
+  int F, I, K;
+  int flag;
+  float scale;
+} dac_pack_desc;
+int dac_op_pack(const dac_pack_desc* d, const float* w, const float* gain, const float* beta, const float* bias,
+                void* const* out, const size_t* cap, size_t* need);
 
 /* Evaluation metrics of config/daclip-sde/test.py:131-196 on the device, handle-less (the
  * caller owns all memory; everything on the current device). out / gt: fp32 [B,C,H,W] RGB,

@@ -45,7 +45,7 @@ def test_conv3x3_kernels_match_naive_reference(dt):
 def test_norm_folded_gemms_match_host_reference():
     """SpatialTransformer norm1 -> q|k|v and norm3 -> GEGLU proj as ONE GEMM each (EPI_LNF: the
     LN gain folded into the weights, the row moments taken from the kernel's own A fragments,
-    engine.cpp Packer::fold_ln) against a host fp64 LayerNorm + GEMM (+ GEGLU) with the exact
+    csrc/pack.h fold_ln) against a host fp64 LayerNorm + GEMM (+ GEGLU) with the exact
     weights, on rows offset by several standard deviations (attention.py:253-261; LN eps 1e-5);
     and proj_in with the GroupNorm(32, eps 1e-6) applied to its A fragments (EPI_GNA) against a
     host GroupNorm + GEMM (attention.py:76-77, 239-241). Bound 1e-2 max-rel: bf16 operands and
@@ -141,7 +141,7 @@ def test_small_grid_ring_depth_bit_identical():
 def test_swapped_geglu_projection_bit_identical():
     """The SpatialTransformer's GEGLU projection (attention.py GEGLU: proj -> x * gelu(gate)) on
     swapped-operand tiles with the register epilogue (weights packed so each lane holds the x and
-    gate accumulators of the same 8 output channels; engine.cpp Packer::geglu) against the
+    gate accumulators of the same 8 output channels; csrc/pack.h geglu_gs_rows) against the
     LDS-epilogue tile on the same bf16 operands, at both UNet shapes (512 -> 2x2048 and
     256 -> 2x1024 on 32x32 x 8 images) and all four swapped tile sizes: bit-identical outputs
     (same ordered MFMA sums and epilogue arithmetic). Timing lines are printed."""

@@ -11,7 +11,7 @@ hook dac_op_conv, against a torch float64 reference written from the definition 
     epi: +bias -> *(1 + scale) + shift -> act -> +res1 -> +res2 -> +bbias;  GEGLU: x * gelu_erf(gate)
 
 The reference works on the exactly representable operands (inputs, weights and residuals rounded
-to T first; split-precision weights are hi + lo). The weight packers of engine.cpp (plain
+to T first; split-precision weights are hi + lo). The weight packers of csrc/pack.h (plain
 [O][kh][kw][Cin], the 7x7 row-tap layout, conv_dual's two layouts, geglu's two row orders) are
 re-implemented here; CPU tests unpack each, and check that the literal packed-K GEMM over the
 arrays handed to the hook (pitches, packed weights, ConvArgs fields) equals the reference.
@@ -229,7 +229,7 @@ CASES = build_cases()
 FAMILIES = sorted({c.fam for c in CASES})
 
 
-# ------------------------------------------------------------------ packers (engine.cpp Packer)
+# ------------------------------------------------------------------ packers (csrc/pack.h; pinned to it by test_pack.py)
 def pack_plain(W):
     """[O][C][kh][kw] -> [O][kh][kw][C] as [O, K]."""
     return W.permute(0, 2, 3, 1).reshape(W.shape[0], -1)

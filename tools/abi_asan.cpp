@@ -1,6 +1,6 @@
 // abi_asan.cpp — argument-validation paths of the C ABI (include/daclip_hip.h) under a host
 // AddressSanitizer build (SURVEY.md §5 "Race detection / sanitizers": a debug build with
-// -fsanitize=address for host code). Built by `make -C da-clip_amd asan`: capi.cpp and
+// -fsanitize=address for host code). Built by `make -C da-clip_amd asan`: capi.cpp, pack.cpp and
 // engine.cpp compiled with `-Xarch_host -fsanitize=address` (device code is not sanitized),
 // linked with the normal kernel objects into this executable, so the ASan runtime comes with
 // the binary (no preload). Every call below must return its documented DAC_E* code without a
@@ -105,6 +105,66 @@ int main() {
     q = cd; q.kh = 7; q.C1 = q.Cin = q.ld1 = 8; q.K = 896; q.cwrap = 1; q.dtype = DAC_F32;
     EXPECT(call(q, dummy, nullptr, dummy, dummy) == DAC_E_ARG);                                  // row-tap dual in fp32
     q = cd; q.kh = 4; q.Hs = 7; q.K = 16 * 64; EXPECT(call(q, dummy, nullptr, dummy, dummy) == DAC_E_ARG);   // odd input
+  }
+  // dac_op_pack (host only): every layout family writes into heap buffers of exactly the queried
+  // sizes, and the refusals come before any buffer is touched.
+  {
+    std::vector<float> w(64 * 64 * 9), g(64, 1.25f), b(192, 0.5f);
+    for (size_t i = 0; i < w.size(); ++i) w[i] = 0.001f * (float)((int)(i * 37 % 1001) - 500);
+    auto run = [&](dac_pack_desc d, const float* gain, const float* beta, const float* bias, int shrink = -1) {
+      size_t need[3] = {0, 0, 0};
+      int rc = dac_op_pack(&d, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, need);
+      if (rc != DAC_OK) return rc;
+      std::vector<std::vector<unsigned char>> buf(3);
+      void* out[3];
+      size_t cap[3];
+      for (int i = 0; i < 3; ++i) {
+        cap[i] = need[i] - (i == shrink ? 1 : 0);
+        buf[i].resize(cap[i]);
+        out[i] = cap[i] ? buf[i].data() : nullptr;
+      }
+      return dac_op_pack(&d, w.data(), gain, beta, bias, out, cap, need);
+    };
+    dac_pack_desc d;
+    auto desc = [&](int layout, int dtype) {
+      std::memset(&d, 0, sizeof d);
+      d.layout = layout; d.dtype = dtype; d.scale = 1.f;
+    };
+    desc(DAC_PACK_CODEC, DAC_FP8); d.O = 100; EXPECT(run(d, nullptr, nullptr, nullptr) == DAC_OK);
+    desc(DAC_PACK_CODEC, DAC_F16); d.O = 100; d.flag = 1; EXPECT(run(d, nullptr, nullptr, nullptr) == DAC_OK);
+    desc(DAC_PACK_EMU_FP16, DAC_F32); d.O = 100; EXPECT(run(d, nullptr, nullptr, nullptr) == DAC_OK);
+    desc(DAC_PACK_CONV, DAC_BF16); d.O = 5; d.C = 6; d.kh = d.kw = 7; d.kwp = 8; d.round = 1;
+    EXPECT(run(d, nullptr, nullptr, nullptr) == DAC_OK);
+    EXPECT(run(d, nullptr, nullptr, nullptr, 0) == DAC_E_ARG);                         // capacity one byte short
+    d.C = 0; EXPECT(run(d, nullptr, nullptr, nullptr) == DAC_E_ARG);
+    desc(DAC_PACK_CONV, DAC_F32); d.O = 5; d.C = 13; d.kh = d.kw = 3; EXPECT(run(d, nullptr, nullptr, nullptr) == DAC_OK);
+    desc(DAC_PACK_DUAL, DAC_F16); d.O = 5; d.C = 6; d.kh = d.kw = 7; d.kwp = 8; EXPECT(run(d, nullptr, nullptr, nullptr) == DAC_OK);
+    desc(DAC_PACK_DUAL, DAC_BF16); d.O = 3; d.C = 64; d.kh = d.kw = 3; EXPECT(run(d, nullptr, nullptr, nullptr) == DAC_OK);
+    d.dtype = DAC_F32; EXPECT(run(d, nullptr, nullptr, nullptr) == DAC_E_ARG);         // 16-bit only
+    desc(DAC_PACK_UPH_ROW, DAC_BF16); d.O = 3; d.C = 12; d.kh = d.kw = 3; EXPECT(run(d, nullptr, nullptr, nullptr) == DAC_OK);
+    desc(DAC_PACK_UPH_COL, DAC_F16); d.O = 3; d.C = 12; d.kh = d.kw = 3; d.round = 1; EXPECT(run(d, nullptr, nullptr, nullptr) == DAC_OK);
+    d.kh = d.kw = 1; EXPECT(run(d, nullptr, nullptr, nullptr) == DAC_E_ARG);           // 3x3 only
+    desc(DAC_PACK_Q8C3, DAC_FP8); d.O = d.C = 64; d.kh = d.kw = 3; EXPECT(run(d, nullptr, nullptr, nullptr) == DAC_OK);
+    d.C = 32; EXPECT(run(d, nullptr, nullptr, nullptr) == DAC_E_ARG);
+    desc(DAC_PACK_GEGLU, DAC_BF16); d.F = 48; d.I = 8; EXPECT(run(d, nullptr, nullptr, b.data()) == DAC_OK);
+    EXPECT(run(d, nullptr, nullptr, nullptr) == DAC_E_ARG);                            // bias required
+    EXPECT(run(d, nullptr, nullptr, b.data(), 2) == DAC_E_ARG);
+    desc(DAC_PACK_GEGLU_GS, DAC_F16); d.F = 96; d.I = 8; EXPECT(run(d, nullptr, nullptr, b.data()) == DAC_OK);
+    d.F = 48; EXPECT(run(d, nullptr, nullptr, b.data()) == DAC_E_ARG);                 // F % 32
+    desc(DAC_PACK_CONCAT, DAC_BF16); d.K = 3; d.O = 4; d.I = 8; d.scale = 0.25f; EXPECT(run(d, nullptr, nullptr, nullptr) == DAC_OK);
+    desc(DAC_PACK_TRANSPOSE, DAC_F32); d.I = 5; d.O = 7; EXPECT(run(d, nullptr, nullptr, nullptr) == DAC_OK);
+    desc(DAC_PACK_FP8, DAC_FP8); d.O = 3; d.K = 192; EXPECT(run(d, nullptr, nullptr, nullptr) == DAC_OK);
+    desc(DAC_PACK_FOLD_LN, DAC_BF16); d.O = 6; d.K = 32; EXPECT(run(d, g.data(), b.data(), b.data()) == DAC_OK);
+    EXPECT(run(d, g.data(), nullptr, nullptr) == DAC_OK);
+    EXPECT(run(d, nullptr, nullptr, nullptr) == DAC_E_ARG);                            // gain required
+    desc(DAC_PACK_LA_FOLD, DAC_F16); d.O = 12; d.C = 16; d.flag = 1; EXPECT(run(d, g.data(), nullptr, nullptr) == DAC_OK);
+    d.O = 8; EXPECT(run(d, g.data(), nullptr, nullptr) == DAC_E_ARG);
+    desc(99, DAC_BF16); d.O = 4; EXPECT(run(d, nullptr, nullptr, nullptr) == DAC_E_ARG);
+    desc(DAC_PACK_CONV, 99); d.O = 4; d.C = 8; d.kh = d.kw = 3; EXPECT(run(d, nullptr, nullptr, nullptr) == DAC_E_ARG);
+    size_t need[3];
+    EXPECT(dac_op_pack(nullptr, w.data(), nullptr, nullptr, nullptr, nullptr, nullptr, need) == DAC_E_ARG);
+    desc(DAC_PACK_CONV, DAC_BF16); d.O = 4; d.C = 8; d.kh = d.kw = 3;
+    EXPECT(dac_op_pack(&d, w.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == DAC_E_ARG);
   }
   // dac_image_metrics: null pointers and unsupported shapes are refused before any device work.
   unsigned char bytes[4] = {0, 0, 0, 0};

@@ -13,6 +13,7 @@
 #include <algorithm>
 #include "../da-clip_amd/csrc/kernels.h"
 #include "../da-clip_amd/csrc/conv_plan.h"
+#include "../da-clip_amd/csrc/pack.h"
 
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e)); exit(1);} } while (0)
 using namespace dac;
@@ -67,45 +68,15 @@ template <typename E> __global__ void ref_conv(ConvArgs a, int kh, int s, int p,
   out[i] = acc;
 }
 
-// ---- fp8 (conv8.hip) check: host e4m3 quantization identical in spirit to engine.cpp.
-static uint8_t f2e4m3(float f) {
-  const uint8_t sign = std::signbit(f) ? 0x80 : 0;
-  const float a = std::fabs(f);
-  if (std::isnan(a)) return 0x7f;
-  if (a >= 464.f) return sign | 0x7e;
-  if (a < std::ldexp(1.f, -6)) { const int q = (int)std::nearbyint(a * 512.f); return sign | (uint8_t)(q >= 8 ? 8 : q); }
-  int e; std::frexp(a, &e);
-  int E = e - 1 + 7, q = (int)std::nearbyint((a / std::ldexp(1.f, e - 1) - 1.f) * 8.f);
-  if (q == 8) { q = 0; ++E; }
-  if (E > 15 || (E == 15 && q == 7)) return sign | 0x7e;
-  return sign | (uint8_t)(E << 3) | (uint8_t)q;
-}
-static float e4m3f(uint8_t b) {
-  const int s = b >> 7, E = (b >> 3) & 15, q = b & 7;
-  const float v = E ? std::ldexp(1.f + q / 8.f, E - 7) : std::ldexp(q / 8.f, -6);
-  return s ? -v : v;
-}
+// Packed operands (folds, MX e4m3 copies, GEGLU orders, 16-bit rounding) come from csrc/pack.h,
+// the functions the engine packs with; 16-bit weights are stored with plain RNE here.
 static float bf2f(bf16 v) { return (float)v; }
 static float bf2f(f16 v) { return (float)v; }
-// Quantize rows of n values in 64-blocks: returns dequantized values (and e4m3 bytes + E8M0).
-static void quant_rows(const std::vector<float>& v, int rows, int n, int np, std::vector<float>& deq,
-                       std::vector<uint8_t>* q8, std::vector<uint8_t>* s8) {
-  deq.assign((size_t)rows * n, 0.f);
-  if (q8) { q8->assign((size_t)rows * np, 0); s8->assign((size_t)rows * (np / 64), 127); }
-  for (int r = 0; r < rows; ++r)
-    for (int b = 0; b * 64 < n; ++b) {
-      float mx = 0.f;
-      for (int k = 64 * b; k < std::min(n, 64 * b + 64); ++k) mx = std::max(mx, std::fabs(v[(size_t)r * n + k]));
-      int e = mx > 0.f ? (int)std::ceil(std::log2(mx / 448.f)) : 0;
-      e = std::min(126, std::max(-126, e));
-      if (s8) (*s8)[(size_t)r * (np / 64) + b] = (uint8_t)(127 + e);
-      for (int k = 64 * b; k < std::min(n, 64 * b + 64); ++k) {
-        const uint8_t q = f2e4m3(v[(size_t)r * n + k] * std::ldexp(1.f, -e));
-        if (q8) (*q8)[(size_t)r * np + k] = q;
-        deq[(size_t)r * n + k] = e4m3f(q) * std::ldexp(1.f, e);
-      }
-    }
+template <typename E> constexpr Store store_of() { return std::is_same<E, f16>::value ? Store::f16 : Store::bf16; }
+template <typename E> static std::vector<uint16_t> rne16(const std::vector<float>& v) {
+  return quantize16(v, 1, 1, store_of<E>(), Round::rne);
 }
+
 // Host direct conv (NHWC x [B][H][W][Cin], w [Cout][kh][kw][Cin]) for the fp8 check.
 static void host_conv(const std::vector<float>& x, const std::vector<float>& w, int B, int H, int W, int Cin,
                       int Cout, int k, int s, int p, std::vector<float>& y, int& Ho, int& Wo) {
@@ -147,10 +118,12 @@ static int fp8_check() {
       for (size_t i = 0; i < nx; ++i) { const size_t m = i / sh.cin, c = i % sh.cin; xf[i] = c == m % 128 ? 1.f : 0.f; xb[i] = (bf16)xf[i]; }
       for (size_t i = 0; i < wf.size(); ++i) wf[i] = (i % K) == (i / K) % sh.cin ? 1.f : 0.f;
     }
-    std::vector<float> xd, wd;
-    std::vector<uint8_t> w8, s8;
-    quant_rows(xf, (int)(nx / sh.cin), sh.cin, sh.cin, xd, nullptr, nullptr);   // per pixel, 64-ch blocks
-    quant_rows(wf, sh.cout, K, Kp, wd, &w8, &s8);
+    // The dequantized operands: x per pixel in 64-channel blocks, as conv8's A loader quantizes it.
+    const int npx = (int)(nx / sh.cin);
+    const std::vector<float> xd = fp8_dequant(make_fp8(xf, npx, sh.cin), npx, sh.cin);
+    const Mx8 wq = make_fp8(wf, sh.cout, K);
+    const std::vector<float> wd = fp8_dequant(wq, sh.cout, K);
+    const std::vector<uint8_t>&w8 = wq.w8, &s8 = wq.s8;
     int Ho, Wo;
     std::vector<float> yq, yf;
     host_conv(xd, wd, sh.B, sh.H, sh.W, sh.cin, sh.cout, sh.k, sh.s, sh.p, yq, Ho, Wo);
@@ -238,19 +211,10 @@ static int lnf_check(int iters) {
     for (auto& v : be) v = 0.2f * rnd();
     for (auto& v : w) v = rnd() * 0.1f;
     for (auto& v : b) v = 0.1f * rnd();
-    // Folded operands (what engine.cpp Packer::fold_ln stores): w' = bf16(w g), cs = sum w'.
-    std::vector<bf16> wf((size_t)N * C);
-    std::vector<float> cs(N), bf(N);
-    for (int n = 0; n < N; ++n) {
-      double c = 0, bb = b[n];
-      for (int k = 0; k < C; ++k) {
-        wf[(size_t)n * C + k] = (bf16)(w[(size_t)n * C + k] * g[k]);
-        c += bf2f(wf[(size_t)n * C + k]);
-        bb += (double)w[(size_t)n * C + k] * be[k];
-      }
-      cs[n] = (float)c;
-      bf[n] = (float)bb;
-    }
+    // Folded operands (pack.h fold_ln): w' = bf16(w g), cs = sum w', bias' = b + w beta.
+    const FoldedLN fo = fold_ln(w, N, C, g.data(), be.data(), b.data(), Store::bf16);
+    const std::vector<uint16_t>& wf = fo.w;
+    const std::vector<float>&cs = fo.cs, &bf = fo.bias;
     // Reference (fp64): LN rows, GEMM with the exact weights, bias, GEGLU pairing.
     std::vector<double> ln((size_t)M * C), ref((size_t)M * NO);
     for (int m = 0; m < M; ++m) {
@@ -561,22 +525,12 @@ static int gns_check() {
 //  then times the pair against the 16-bit pair at B = 8, 256^2 (the bench level) and 128^2.
 static void q8_weights(const std::vector<float>& w, std::vector<uint8_t>& w8, std::vector<uint8_t>& s8,
                        std::vector<float>& deq) {
-  // w: [64][3][3][64] -> e4m3 [64][9][64] + E8M0 [64][9][2] (engine.cpp Packer::make_q8c3)
-  w8.assign(64 * 576, 0); s8.assign(64 * 18, 127); deq.assign(64 * 576, 0.f);
-  for (int n = 0; n < 64; ++n)
-    for (int t = 0; t < 9; ++t)
-      for (int h = 0; h < 2; ++h) {
-        const size_t o = (size_t)n * 576 + t * 64 + 32 * h;
-        float mx = 0.f;
-        for (int c = 0; c < 32; ++c) mx = std::max(mx, std::fabs(w[o + c]));
-        int e = mx > 0.f ? (int)std::ceil(std::log2((double)mx / 448.0)) : 0;
-        e = std::min(126, std::max(-126, e));
-        s8[(size_t)n * 18 + t * 2 + h] = (uint8_t)(127 + e);
-        for (int c = 0; c < 32; ++c) {
-          w8[o + c] = f2e4m3(std::ldexp(w[o + c], -e));
-          deq[o + c] = std::ldexp(e4m3f(w8[o + c]), e);
-        }
-      }
+  // w: [64][3][3][64] -> e4m3 [64][9][64] + E8M0 [64][9][2] (pack.h make_q8c3), and the values
+  // they stand for.
+  const Mx8 m = make_q8c3(w);
+  w8 = m.w8; s8 = m.s8;
+  deq.resize(w8.size());
+  for (size_t i = 0; i < w8.size(); ++i) deq[i] = std::ldexp(e4m3f_host(w8[i]), (int)s8[i / 32] - 127);
 }
 static int q8_check(int iters) {
   int fails = 0;
@@ -662,10 +616,10 @@ static int q8_check(int iters) {
           float mx = 0.f, mq = 0.f;
           for (int c = 32 * hf; c < 32 * hf + 32; ++c) {
             const size_t i = (size_t)m * 64 + c;
-            const float y = bf2f(h16[i]), d = std::ldexp(e4m3f(h8[i]), e);
+            const float y = bf2f(h16[i]), d = std::ldexp(e4m3f_host(h8[i]), e);
             hd[i] = d;
             mx = std::max(mx, std::fabs(y));
-            mq = std::max(mq, std::fabs(e4m3f(h8[i])));
+            mq = std::max(mq, std::fabs(e4m3f_host(h8[i])));
             if (!(std::fabs(d - y) <= 0.0703f * std::fabs(y) + std::ldexp(1.f, e - 8))) {
               if (bad_v < 4) printf("   h m=%d c=%d got %g want %g (e %d)\n", m, c, d, y, e);
               ++bad_v;
@@ -760,33 +714,14 @@ template <typename E> static int uph_check(int iters, const char* tn) {
     const int Ho = 2 * sh.Hs, Wo = 2 * sh.Ws, M = sh.B * Ho * Wo, C = sh.cin, N = sh.cout;
     uint32_t hs = 4242 + C;
     auto rnd = [&]() { hs = hs * 1664525u + 1013904223u; return ((hs >> 8) & 0xffff) / 65535.f - 0.5f; };
-    std::vector<E> xb((size_t)sh.B * sh.Hs * sh.Ws * C), wb((size_t)N * 9 * C), pb((size_t)N * 12 * C),
-        qb((size_t)N * 16 * C);
+    std::vector<E> xb((size_t)sh.B * sh.Hs * sh.Ws * C);
     std::vector<float> wf((size_t)N * 9 * C), bias(N);
     for (auto& v : xb) v = (E)(2.f * rnd());
     for (auto& v : wf) v = 0.05f * rnd();
     for (auto& v : bias) v = 0.1f * rnd();
-    for (size_t i = 0; i < wf.size(); ++i) wb[i] = (E)wf[i];
-    const size_t R = (size_t)3 * C;
-    for (int o = 0; o < N; ++o)
-      for (size_t k = 0; k < R; ++k) {
-        const float* w = &wf[(size_t)o * 3 * R];
-        E* d = &pb[(size_t)o * 4 * R];
-        d[k] = (E)w[k]; d[R + k] = (E)(w[R + k] + w[2 * R + k]);
-        d[2 * R + k] = (E)(w[k] + w[R + k]); d[3 * R + k] = (E)w[2 * R + k];
-      }
-    {
-      static const int lo[4] = {0, 1, 0, 2}, hi[4] = {0, 2, 1, 2};
-      for (int o = 0; o < N; ++o)
-        for (int rs = 0; rs < 4; ++rs)
-          for (int cs = 0; cs < 4; ++cs)
-            for (int c = 0; c < C; ++c) {
-              float v = 0.f;
-              for (int kh = lo[rs]; kh <= hi[rs]; ++kh)
-                for (int kw = lo[cs]; kw <= hi[cs]; ++kw) v += wf[(((size_t)o * 3 + kh) * 3 + kw) * C + c];
-              qb[(((size_t)o * 4 + rs) * 4 + cs) * C + c] = (E)v;
-            }
-    }
+    // The plain [N][3][3][C] weights and their row- and row+column-phase folds (pack.h).
+    const std::vector<uint16_t> wb = rne16<E>(wf), pb = rne16<E>(fold_row_phase(wf, N, C)),
+                                qb = rne16<E>(fold_rowcol_phase(wf, N, C));
     void *dx, *dw, *dp, *dq, *dz, *dy0, *dy1, *dy2; float* db;
     CK(hipMalloc(&dq, qb.size() * 2)); CK(hipMalloc(&dy2, (size_t)M * N * 2));
     CK(hipMemcpy(dq, qb.data(), qb.size() * 2, hipMemcpyHostToDevice));
@@ -1071,14 +1006,9 @@ static int gsw_check(int iters) {
     auto rnd = [&]() { st = st * 1664525u + 1013904223u; return ((st >> 8) / 16777216.f - 0.5f); };
     for (auto& v : wr) v = 0.2f * rnd();
     for (auto& v : br) v = rnd();
-    std::vector<bf16> wo((size_t)2 * F * I), wg((size_t)2 * F * I);
-    std::vector<float> bo(2 * F), bg(2 * F);
-    for (int r = 0; r < 2 * F; ++r) {
-      const int g = r / 32, s2 = r % 32, so = s2 < 16 ? 16 * g + s2 : F + 16 * g + (s2 - 16);
-      const int G = r / 64, lg = (r % 64) / 16, e = r % 16, sg = (e < 8 ? 0 : F) + 32 * G + 8 * lg + (e & 7);
-      for (int k = 0; k < I; ++k) { wo[(size_t)r * I + k] = (bf16)wr[(size_t)so * I + k]; wg[(size_t)r * I + k] = (bf16)wr[(size_t)sg * I + k]; }
-      bo[r] = br[so]; bg[r] = br[sg];
-    }
+    const std::vector<int> ro = geglu_rows(F), rg = geglu_gs_rows(F);      // pack.h: both row orders
+    const std::vector<uint16_t> wo = rne16<bf16>(gather_rows(wr.data(), ro, I)), wg = rne16<bf16>(gather_rows(wr.data(), rg, I));
+    const std::vector<float> bo = gather_rows(br.data(), ro, 1), bg = gather_rows(br.data(), rg, 1);
     bf16 *x, *dwo, *dwg, *y; float *dbo, *dbg; void* zero;
     CK(hipMalloc(&x, npx * I * 2)); CK(hipMalloc(&dwo, wo.size() * 2)); CK(hipMalloc(&dwg, wg.size() * 2));
     CK(hipMalloc(&y, npx * F * 2)); CK(hipMalloc(&dbo, bo.size() * 4)); CK(hipMalloc(&dbg, bg.size() * 4));
