@@ -21,10 +21,6 @@ namespace dac {
 // / outputs (after each kernel) are rounded to bf16, emulating the bf16 engine one part at a time.
 enum Role : int { R_INIT = 1, R_RB = 2, R_SAMP = 4, R_LA = 8, R_ST = 16, R_FINAL = 32, R_FIN_RB = 64,
                   R_MID = 128, R_OTHER = 256 };
-static int env_mask(const char* n) {
-  const char* v = getenv(n);
-  return v ? (int)strtol(v, nullptr, 0) : 0;
-}
 // Per-image split-K count for the 3x3 convs (and split-K for the 1x1 GEMMs) of the UNet levels of
 // at most 1024 pixels per image (the 32x32 level at 256^2), set by UNetNet::forward from the
 // handle's policy: Wild-IR (scale-0.5) handles, whose configs[3] slice is 2 images per GPU, use 4;
@@ -36,7 +32,6 @@ struct SplitKScope {
   explicit SplitKScope(int k) : prev(g_splitk) { g_splitk = k; }
   ~SplitKScope() { g_splitk = prev; }
 };
-static int emu_a() { static const int m = env_mask("DAC_EMU_A"); return m; }
 static thread_local int g_role = R_OTHER;
 struct RoleScope {
   int prev;
@@ -58,7 +53,49 @@ static int key_role(const std::string& k) {
 }
 template <typename T>
 static void emu_round(const Run& r, void* y, int ld, size_t rows, int C);
+// ============================================================================= runtime switches
+// Every environment variable this file reads: one accessor each, with its read time. (The packing
+// switches are PackKnobs in pack.h, the kernel-selection ones ConvKnobs in conv_plan.h.)
+static bool env_on(const char* v, bool dflt) { return v ? atoi(v) != 0 : dflt; }
+static long long env_num(const char* v, long long dflt) { return v ? atoll(v) : dflt; }
+static bool env_is1(const char* v) { return v && v[0] == '1'; }
+static bool env_is(const char* v, const char* want) { return v && !strcmp(v, want); }
+static int env_mask(const char* v) { return v ? (int)strtol(v, nullptr, 0) : 0; }
+
+// ---- read once per process
+// DAC_EMU_A: the precision probe's activation role mask (above; any strtol base).
+static int emu_a() { static const int m = env_mask(getenv("DAC_EMU_A")); return m; }
+// DAC_Q8=0: fp8 handles keep the 16-bit ResBlock pairs (A/B switch for the e4m3 block2 path).
+static bool q8_on() { static const bool on = env_on(getenv("DAC_Q8"), true); return on; }
 // DAC_NO_RES_FUSE=1: run each ResBlock res_conv as its own launch (A/B switch).
+static bool no_res_fuse() { static const bool on = env_on(getenv("DAC_NO_RES_FUSE"), false); return on; }
+// DAC_LA256=0: the C = 256 LinearAttention (the 64x64 level) on the unfused chain, for A/B.
+static bool la256_on() { static const bool on = env_on(getenv("DAC_LA256"), true); return on; }
+// DAC_F16_EDGES=1: f16 handles take the bf16 handles' split-precision edge weights (precision
+// probe, tools/gpu_probe16.sh).
+static bool f16_edges() { static const bool on = env_on(getenv("DAC_F16_EDGES"), false); return on; }
+// DAC_DUP1X1=1 (diagnostic): the 32x32-level 1x1 GEMMs run twice back to back (idempotent: the
+// output never aliases an input), to separate a launch's cold-input cost in the trace.
+static bool dup1x1() { static const bool on = env_on(getenv("DAC_DUP1X1"), false); return on; }
+// DAC_SPLITK_PX: the largest level, in pixels per image, whose 3x3 convs split K under g_splitk.
+static long splitk_px() { static const long n = (long)env_num(getenv("DAC_SPLITK_PX"), 1024); return n; }
+// DAC_SPLITK32_1X1=0: the UNet's 1x1 GEMMs stay unsplit under g_splitk.
+static bool splitk32_1x1() { static const bool on = env_on(getenv("DAC_SPLITK32_1X1"), true); return on; }
+// DAC_SPLITK32=k: g_splitk for every handle (0 = off); unset (-1): the handle's policy.
+static int splitk32() { static const int k = (int)env_num(getenv("DAC_SPLITK32"), -1); return k; }
+// DAC_SPLIT_LVL: first level, counted from the bottom, of the UNet section that runs as concurrent
+// branches (0 = off); DAC_SPLIT_N: how many branches.
+static int split_lvl() { static const int n = (int)env_num(getenv("DAC_SPLIT_LVL"), 3); return n; }
+static int split_n() { static const int n = (int)env_num(getenv("DAC_SPLIT_N"), 2); return n; }
+// DAC_POISON=1: fill fresh workspace with 0xFF bytes (NaN in f32/bf16) so any read-before-write
+// shows up as a NaN in the outputs (debug aid).
+static bool poison() { static const bool on = env_is1(getenv("DAC_POISON")); return on; }
+// DAC_NO_GRAPH=1: the sampler loops are enqueued eagerly instead of captured and replayed.
+static bool no_graph() { static const bool on = env_is1(getenv("DAC_NO_GRAPH")); return on; }
+// DAC_FP8_BASE=f16: fp8 handles run every non-e4m3 layer in IEEE half instead of bf16.
+static bool fp8_base_f16() { static const bool on = env_is(getenv("DAC_FP8_BASE"), "f16"); return on; }
+
+// ---- read at every use
 // Norm folding switches (DAC_FOLD, a bit mask read when weights are packed and per forward):
 //   1 norm1 LayerNorm folded into the SpatialTransformer's q|k|v GEMM
 //   2 (unused: norm3 folded into the GEGLU proj measured slower and, in fp16 handles, not
@@ -68,20 +105,14 @@ static void emu_round(const Run& r, void* y, int ld, size_t rows, int C);
 //  16 ... with its statistics taken by the PreNorm LayerNorm kernel (needs 8)
 // The default is the set measured faster in the network.
 constexpr int kFoldDefault = 1 | 4 | 8 | 16;
-static int fold_mask() {
-  const char* e = getenv("DAC_FOLD");
-  return e ? atoi(e) : kFoldDefault;
-}
-static bool fold_on(int bit) { return (fold_mask() & bit) != 0; }
-// DAC_Q8=0: fp8 handles keep the 16-bit ResBlock pairs (A/B switch for the e4m3 block2 path).
-static bool q8_on() {
-  static const bool on = !getenv("DAC_Q8") || atoi(getenv("DAC_Q8")) != 0;
-  return on;
-}
-static bool no_res_fuse() {
-  static const int v = getenv("DAC_NO_RES_FUSE") ? atoi(getenv("DAC_NO_RES_FUSE")) : 0;
-  return v != 0;
-}
+static bool fold_on(int bit) { return ((int)env_num(getenv("DAC_FOLD"), kFoldDefault) & bit) != 0; }
+// DAC_VIT_GEMM=0 (when weights are packed): the ViT patch stem stays the direct conv.
+static bool vit_gemm_on() { return env_on(getenv("DAC_VIT_GEMM"), true); }
+// DAC_FUSE_PREP=0 (per recording): every step keeps its own unet_prep launch.
+static bool fuse_prep_on() { return env_on(getenv("DAC_FUSE_PREP"), true); }
+// DAC_TILED_MAX_NODES (per tiled call that captures): the largest captured loop still instantiated
+// as a graph (tests compare the two forms).
+static size_t tiled_max_nodes(size_t dflt) { return (size_t)env_num(getenv("DAC_TILED_MAX_NODES"), (long long)dflt); }
 
 // ============================================================================= weights
 const HostW* WStore::get(const std::string& key, std::vector<int64_t> shape) {
@@ -364,10 +395,9 @@ void conv_call(Run& r, const ConvW& cw, const void* x1, int ld1, int C1, const v
   const bool use8 = sizeof(T) == 2 && cw.w8 && conv8_ok(a, cw.kh, cw.kw, stride, pad);
   // Per-image split-K at the small levels (g_splitk, UNetNet::forward): 3x3 convs over ks Cin
   // ranges; the count depends on one image's shape and the handle's policy, never on B.
-  static const long split_px = getenv("DAC_SPLITK_PX") ? atol(getenv("DAC_SPLITK_PX")) : 1024;
   int ks3 = 0;
   if (g_splitk > 1 && cw.kh == 3 && cw.kw == 3 && stride == 1 && pad == 1 && !up && !use8 && !a.uph &&
-      (long)a.Ho * a.Wo <= split_px && a.Ho > 1) {
+      (long)a.Ho * a.Wo <= splitk_px() && a.Ho > 1) {
     ConvArgs q = a;
     q.w2 = nullptr; q.bias2 = nullptr; q.y2 = nullptr; q.w2_dual = 0; q.ldy2 = 0;
     ks3 = conv3_split_k(q, (int)sizeof(T), g_splitk);
@@ -390,9 +420,8 @@ void conv_call(Run& r, const ConvW& cw, const void* x1, int ld1, int C1, const v
   }
   // Split-K (the small-M 1x1 GEMMs: ViT / text tower linears, and the UNet's small levels under
   // g_splitk): fp32 partials from the arena; the count follows one image's rows.
-  static const bool split1 = !getenv("DAC_SPLITK32_1X1") || atoi(getenv("DAC_SPLITK32_1X1")) != 0;
   const long srows = e.split_rows > 0 ? e.split_rows
-                     : (split1 && g_splitk > 1 && a.Ho > 1 && a.Wo > 1 && (long)a.Ho * a.Wo <= 1024) ? (long)a.Ho * a.Wo : 0;
+                     : (splitk32_1x1() && g_splitk > 1 && a.Ho > 1 && a.Wo > 1 && (long)a.Ho * a.Wo <= 1024) ? (long)a.Ho * a.Wo : 0;
   if (srows > 0 && cw.kh == 1 && cw.kw == 1 && stride == 1 && pad == 0 && !use8 && !e.fuse1x1) {
     const int ks = conv_split_k(a, (int)sizeof(T), srows);
     if (ks > 1) {
@@ -423,10 +452,7 @@ void conv_call(Run& r, const ConvW& cw, const void* x1, int ld1, int C1, const v
     if constexpr (sizeof(T) == 2) conv8<T>(a, cw.kh, cw.kw, stride, pad, cw.w8, cw.ws8, cw.kp8, r.st);
   } else {
     conv<T>(a, cw.kh, cw.kw, stride, pad, r.st);
-    // Diagnostic (DAC_DUP1X1=1): the 32x32-level 1x1 GEMMs run twice back to back (idempotent:
-    // the output never aliases an input), to separate a launch's cold-input cost in the trace.
-    static const bool dup = getenv("DAC_DUP1X1") && atoi(getenv("DAC_DUP1X1")) != 0;
-    if (dup && cw.kh == 1 && a.Ho * a.Wo <= 1024 && a.Ho * a.Wo >= 256 && a.ksplit <= 1) conv<T>(a, cw.kh, cw.kw, stride, pad, r.st);
+    if (dup1x1() && cw.kh == 1 && a.Ho * a.Wo <= 1024 && a.Ho * a.Wo >= 256 && a.ksplit <= 1) conv<T>(a, cw.kh, cw.kw, stride, pad, r.st);
   }
   emu_round<T>(r, y, ldy, (size_t)M, cw.cout);
   if (fused) emu_round<T>(r, e.y2, e.ldy2, (size_t)M, cw.cout);
@@ -687,13 +713,9 @@ struct UNetNet {
     return a;
   }
 
-  // Split-precision (hi | lo) edge weights: bf16 handles (and fp8, whose activations are bf16).
-  // DAC_F16_EDGES=1: the same split for f16 handles (precision probe, tools/gpu_probe16.sh).
-  static bool split_edges_f() {
-    if (std::is_same<T, bf16>::value) return true;
-    static const bool f16e = sizeof(T) == 2 && getenv("DAC_F16_EDGES") && atoi(getenv("DAC_F16_EDGES")) != 0;
-    return f16e;
-  }
+  // Split-precision (hi | lo) edge weights: bf16 handles (and fp8, whose activations are bf16),
+  // and f16 handles under f16_edges().
+  static bool split_edges_f() { return std::is_same<T, bf16>::value || (sizeof(T) == 2 && f16_edges()); }
   void load(Packer<T>& P) {
     ss_total = cc_total = n_st = 0;
     if (degra) prompt = P.f32("prompt", {1, tdim});
@@ -970,10 +992,8 @@ struct UNetNet {
     join();
   }
   bool la_fused(const LA& la, int C) const {
-    // C = 256 (the 64x64 level) takes the fused pair too on 16-bit handles (DAC_LA256=0: the
-    // unfused chain, for A/B).
-    static const bool la256 = !getenv("DAC_LA256") || atoi(getenv("DAC_LA256")) != 0;
-    return la.wqkv_g && (C == 64 || C == 128 || (C == 256 && sizeof(T) == 2 && la256));
+    // C = 256 (the 64x64 level) takes the fused pair too on 16-bit handles (la256_on()).
+    return la.wqkv_g && (C == 64 || C == 128 || (C == 256 && sizeof(T) == 2 && la256_on()));
   }
   // Fused (linattn.hip): context pass over x, then one apply pass x -> y (LN, q projection and
   // softmax, per-image to_out, its LayerNorm and the Residual).
@@ -1147,60 +1167,72 @@ struct UNetNet {
     return n + (s - n % s) % s;
   }
 
+  // The level walk's state: the current activation of B images at h x w, this step's tables and
+  // the skip stack the down levels push and the up levels pop.
+  struct Walk {
+    const void* cur; int B, h, w; const float *ss, *cc;
+    std::vector<std::pair<const void*, int>> hs;
+  };
+  // downs[i0, i1).
+  void down(Run& r, Walk& k, int i0, int i1) {
+    for (int i = i0; i < i1; ++i) {
+      const auto [din, dout] = levels[i];
+      Level& L = downs[i];
+      g_role = R_RB;
+      k.cur = resblock(r, L.b1, k.cur, din, nullptr, 0, k.B, k.h, k.w, k.ss);
+      k.hs.push_back({k.cur, din});
+      k.cur = resblock(r, L.b2, k.cur, din, nullptr, 0, k.B, k.h, k.w, k.ss);
+      k.cur = attn(r, L.at, k.cur, din, k.B, k.h, k.w, k.cc);
+      g_role = R_SAMP;
+      k.hs.push_back({k.cur, din});
+      if (i != depth - 1) {
+        T* y = r.alloc<T>((size_t)k.B * (k.h / 2) * (k.w / 2) * dout);
+        conv_call<T>(r, L.samp, k.cur, din, din, nullptr, 0, k.B, k.h, k.w, 0, 2, 1, y, dout, Epi());
+        k.h /= 2; k.w /= 2;
+        k.cur = y;
+      } else {
+        T* y = r.alloc<T>((size_t)k.B * k.h * k.w * dout);
+        conv_call<T>(r, L.samp, k.cur, din, din, nullptr, 0, k.B, k.h, k.w, 0, 1, 1, y, dout, Epi());
+        k.cur = y;
+      }
+    }
+  }
+  void middle(Run& r, Walk& k) {
+    const int mid = levels.back().second;
+    g_role = R_MID;
+    k.cur = resblock(r, mid1, k.cur, mid, nullptr, 0, k.B, k.h, k.w, k.ss);
+    k.cur = attn(r, mid_attn, k.cur, mid, k.B, k.h, k.w, k.cc);
+    k.cur = resblock(r, mid2, k.cur, mid, nullptr, 0, k.B, k.h, k.w, k.ss);
+  }
+  // ups[j0, j1); yout: where the last sampling conv writes instead of a fresh arena buffer.
+  void up(Run& r, Walk& k, int j0, int j1, T* yout = nullptr) {
+    for (int j = j0; j < j1; ++j) {
+      const int i = depth - 1 - j;
+      const auto [din, dout] = levels[i];
+      Level& L = ups[j];
+      auto sk = k.hs.back(); k.hs.pop_back();
+      g_role = R_RB;
+      k.cur = resblock(r, L.b1, k.cur, dout, sk.first, sk.second, k.B, k.h, k.w, k.ss);
+      sk = k.hs.back(); k.hs.pop_back();
+      k.cur = resblock(r, L.b2, k.cur, dout, sk.first, sk.second, k.B, k.h, k.w, k.ss);
+      k.cur = attn(r, L.at, k.cur, dout, k.B, k.h, k.w, k.cc);
+      g_role = R_SAMP;
+      const int u = i != 0;                           // Upsample: nearest 2x, then the 3x3
+      T* y = yout && j == j1 - 1 ? yout : r.alloc<T>((size_t)k.B * (k.h << u) * (k.w << u) * din);
+      conv_call<T>(r, L.samp, k.cur, dout, dout, nullptr, 0, k.B, k.h, k.w, u, 1, 1, y, din, Epi());
+      k.h <<= u; k.w <<= u;
+      k.cur = y;
+    }
+  }
+
   // Levels sl .. depth-1 for images [0, B) of the pointers given: downs[sl..] (their skips stay
   // inside), the middle blocks, ups[..depth-1-sl], the last sampling conv writing yout
   // (B x (2h x 2w) x Cin of level sl; same resolution when sl == 0).
   void section(Run& r, int sl, const void* cur, int B, int h, int w, const float* ss, const float* cc, T* yout) {
-    std::vector<std::pair<const void*, int>> hs;
-    for (int i = sl; i < depth; ++i) {
-      const auto [din, dout] = levels[i];
-      Level& L = downs[i];
-      g_role = R_RB;
-      cur = resblock(r, L.b1, cur, din, nullptr, 0, B, h, w, ss);
-      hs.push_back({cur, din});
-      cur = resblock(r, L.b2, cur, din, nullptr, 0, B, h, w, ss);
-      cur = attn(r, L.at, cur, din, B, h, w, cc);
-      g_role = R_SAMP;
-      hs.push_back({cur, din});
-      if (i != depth - 1) {
-        T* y = r.alloc<T>((size_t)B * (h / 2) * (w / 2) * dout);
-        conv_call<T>(r, L.samp, cur, din, din, nullptr, 0, B, h, w, 0, 2, 1, y, dout, Epi());
-        h /= 2; w /= 2;
-        cur = y;
-      } else {
-        T* y = r.alloc<T>((size_t)B * h * w * dout);
-        conv_call<T>(r, L.samp, cur, din, din, nullptr, 0, B, h, w, 0, 1, 1, y, dout, Epi());
-        cur = y;
-      }
-    }
-    const int mid = levels.back().second;
-    g_role = R_MID;
-    cur = resblock(r, mid1, cur, mid, nullptr, 0, B, h, w, ss);
-    cur = attn(r, mid_attn, cur, mid, B, h, w, cc);
-    cur = resblock(r, mid2, cur, mid, nullptr, 0, B, h, w, ss);
-    for (int j = 0; j < depth - sl; ++j) {
-      const int i = depth - 1 - j;
-      const auto [din, dout] = levels[i];
-      Level& L = ups[j];
-      auto sk = hs.back(); hs.pop_back();
-      g_role = R_RB;
-      cur = resblock(r, L.b1, cur, dout, sk.first, sk.second, B, h, w, ss);
-      sk = hs.back(); hs.pop_back();
-      cur = resblock(r, L.b2, cur, dout, sk.first, sk.second, B, h, w, ss);
-      cur = attn(r, L.at, cur, dout, B, h, w, cc);
-      g_role = R_SAMP;
-      const bool last = j == depth - 1 - sl;
-      if (i != 0) {
-        T* y = last ? yout : r.alloc<T>((size_t)B * (2 * h) * (2 * w) * din);
-        conv_call<T>(r, L.samp, cur, dout, dout, nullptr, 0, B, h, w, 1, 1, 1, y, din, Epi());
-        h *= 2; w *= 2;
-        cur = y;
-      } else {
-        T* y = last ? yout : r.alloc<T>((size_t)B * h * w * din);
-        conv_call<T>(r, L.samp, cur, dout, dout, nullptr, 0, B, h, w, 0, 1, 1, y, din, Epi());
-        cur = y;
-      }
-    }
+    Walk k{cur, B, h, w, ss, cc, {}};
+    down(r, k, sl, depth);
+    middle(r, k);
+    up(r, k, 0, depth - sl, yout);
   }
 
   // One forward. ss: [B][ss_total] of this step; out: [B*Hp*Wp][ldo] (channels < out_nc).
@@ -1217,52 +1249,22 @@ struct UNetNet {
     // Roles are assigned per section below; this scope restores the caller's role when the
     // forward returns (ViT / encoder calls on the thread are unaffected).
     RoleScope rs_init(R_INIT);
-    static const int splitk_env = getenv("DAC_SPLITK32") ? atoi(getenv("DAC_SPLITK32")) : -1;
-    SplitKScope sks(splitk_env >= 0 ? splitk_env : (half ? 4 : 0));
+    SplitKScope sks(splitk32() >= 0 ? splitk32() : (half ? 4 : 0));
     conv_call<T>(r, init_conv, xin, 8, 8, nullptr, 0, B, Hp, Wp, 0, 1, 3, x0, nf, Epi());
-    std::vector<std::pair<const void*, int>> hs;
-    const void* cur = x0;
-    int h = Hp, w = Wp;
+    Walk k{x0, B, Hp, Wp, ss, cc, {}};
     if (half) {                                   // Wild-IR: levels run at half resolution
       T* xd = r.alloc<T>((size_t)B * (Hp / 2) * (Wp / 2) * nf);
       conv_call<T>(r, half_down, x0, nf, nf, nullptr, 0, B, Hp, Wp, 0, 2, 1, xd, nf, Epi());
-      cur = xd;
-      h = Hp / 2; w = Wp / 2;
+      k.cur = xd;
+      k.h = Hp / 2; k.w = Wp / 2;
     }
-    // Section split (DAC_SPLIT_LVL: first level of the section, counted from the bottom, 0 = off;
-    // DAC_SPLIT_N: branches).
-    static const int split_lvl = getenv("DAC_SPLIT_LVL") ? atoi(getenv("DAC_SPLIT_LVL")) : 3;
-    static const int split_n = getenv("DAC_SPLIT_N") ? atoi(getenv("DAC_SPLIT_N")) : 2;
-    const int nbr = std::min({split_n, B, 1 + Run::kSide});
-    const bool split = split_lvl > 0 && nbr >= 2 && r.side[nbr - 2];
-    const int sl = split ? std::max(0, depth - split_lvl) : depth;
-    for (int i = 0; i < sl; ++i) {
-      const auto [din, dout] = levels[i];
-      Level& L = downs[i];
-      g_role = R_RB;
-      cur = resblock(r, L.b1, cur, din, nullptr, 0, B, h, w, ss);
-      hs.push_back({cur, din});
-      cur = resblock(r, L.b2, cur, din, nullptr, 0, B, h, w, ss);
-      cur = attn(r, L.at, cur, din, B, h, w, cc);
-      g_role = R_SAMP;
-      hs.push_back({cur, din});
-      if (i != depth - 1) {
-        T* y = r.alloc<T>((size_t)B * (h / 2) * (w / 2) * dout);
-        conv_call<T>(r, L.samp, cur, din, din, nullptr, 0, B, h, w, 0, 2, 1, y, dout, Epi());
-        h /= 2; w /= 2;
-        cur = y;
-      } else {
-        T* y = r.alloc<T>((size_t)B * h * w * dout);
-        conv_call<T>(r, L.samp, cur, din, din, nullptr, 0, B, h, w, 0, 1, 1, y, dout, Epi());
-        cur = y;
-      }
-    }
+    // Section split: split_lvl() is the first level of the section, split_n() its branches.
+    const int nbr = std::min({split_n(), B, 1 + Run::kSide});
+    const bool split = split_lvl() > 0 && nbr >= 2 && r.side[nbr - 2];
+    const int sl = split ? std::max(0, depth - split_lvl()) : depth;
+    down(r, k, 0, sl);
     if (!split) {
-      const int mid = levels.back().second;
-      g_role = R_MID;
-      cur = resblock(r, mid1, cur, mid, nullptr, 0, B, h, w, ss);
-      cur = attn(r, mid_attn, cur, mid, B, h, w, cc);
-      cur = resblock(r, mid2, cur, mid, nullptr, 0, B, h, w, ss);
+      middle(r, k);
     } else {
       // The lowest split_lvl levels (by default three: the 128x128, 64x64 and 32x32 levels at
       // 256^2, i.e. downs[1..3], the middle blocks, ups[0..2]) have small, latency-bound kernels
@@ -1272,50 +1274,29 @@ struct UNetNet {
       // other. Every kernel is per-image (batch-invariant): the outputs are bit-identical to one
       // full-batch branch. Output: the section's last sampling conv, all images.
       const int C0 = levels[sl].first;
-      const int h0 = h, w0 = w;
-      const size_t px = (size_t)h * w;
-      if (sl != 0) { h *= 2; w *= 2; }
-      const size_t pxo = (size_t)h * w;
+      const int h0 = k.h, w0 = k.w;
+      const size_t px = (size_t)h0 * w0;
+      if (sl != 0) { k.h *= 2; k.w *= 2; }
+      const size_t pxo = (size_t)k.h * k.w;
       T* y = r.alloc<T>((size_t)B * pxo * C0);
       branches(r, B, nbr, [&](Run& rk, int b0, int nb) {
-        section(rk, sl, static_cast<const T*>(cur) + b0 * px * C0, nb, h0, w0,
+        section(rk, sl, static_cast<const T*>(k.cur) + b0 * px * C0, nb, h0, w0,
                 ss ? ss + (size_t)b0 * ss_total : nullptr, cc ? cc + (size_t)b0 * cc_total : nullptr,
                 y + b0 * pxo * C0);
       });
-      cur = y;
+      k.cur = y;
     }
-    for (int j = depth - sl; j < depth; ++j) {
-      const int i = depth - 1 - j;
-      const auto [din, dout] = levels[i];
-      Level& L = ups[j];
-      auto sk = hs.back(); hs.pop_back();
-      g_role = R_RB;
-      cur = resblock(r, L.b1, cur, dout, sk.first, sk.second, B, h, w, ss);
-      sk = hs.back(); hs.pop_back();
-      cur = resblock(r, L.b2, cur, dout, sk.first, sk.second, B, h, w, ss);
-      cur = attn(r, L.at, cur, dout, B, h, w, cc);
-      g_role = R_SAMP;
-      if (i != 0) {
-        T* y = r.alloc<T>((size_t)B * (2 * h) * (2 * w) * din);
-        conv_call<T>(r, L.samp, cur, dout, dout, nullptr, 0, B, h, w, 1, 1, 1, y, din, Epi());
-        h *= 2; w *= 2;
-        cur = y;
-      } else {
-        T* y = r.alloc<T>((size_t)B * h * w * din);
-        conv_call<T>(r, L.samp, cur, dout, dout, nullptr, 0, B, h, w, 0, 1, 1, y, din, Epi());
-        cur = y;
-      }
-    }
+    up(r, k, depth - sl, depth);
     if (half) {
       T* xu = r.alloc<T>((size_t)B * Hp * Wp * nf);
-      conv_call<T>(r, half_up, cur, nf, nf, nullptr, 0, B, h, w, 1, 1, 1, xu, nf, Epi());
-      cur = xu;
-      h = Hp; w = Wp;
+      conv_call<T>(r, half_up, k.cur, nf, nf, nullptr, 0, B, k.h, k.w, 1, 1, 1, xu, nf, Epi());
+      k.cur = xu;
+      k.h = Hp; k.w = Wp;
     }
     g_role = R_FIN_RB;
-    cur = resblock(r, fin, cur, nf, x0, nf, B, h, w, ss);
+    k.cur = resblock(r, fin, k.cur, nf, x0, nf, B, k.h, k.w, ss);
     g_role = R_FINAL;
-    conv_call<T>(r, final_conv, cur, nf, nf, nullptr, 0, B, h, w, 0, 1, 1, out, ldo, Epi());
+    conv_call<T>(r, final_conv, k.cur, nf, nf, nullptr, 0, B, k.h, k.w, 0, 1, 1, out, ldo, Epi());
   }
 };
 
@@ -1395,7 +1376,7 @@ struct VitNet {
     t.conv1 = Pk.conv(p + "conv1.weight", D, 3, P, P);
     const int K = 3 * P * P;
     const HostW* w1 = t.conv1.w ? Pk.ws.get(p + "conv1.weight", {D, 3, P, P}) : nullptr;
-    if (K % 64 == 0 && w1 && !(getenv("DAC_VIT_GEMM") && atoi(getenv("DAC_VIT_GEMM")) == 0)) {
+    if (K % 64 == 0 && w1 && vit_gemm_on()) {
       // [D][P][P][3]: the same weights without the padding channels, as one GEMM operand.
       const std::vector<float> q = pack_ohwi(w1->v.data(), D, 3, P, P, P, 3);
       ConvW& g = t.conv1g;
@@ -1548,8 +1529,8 @@ class EngineT : public Engine {
   ~EngineT() override {
     clear_graphs();
     if (arena.base) (void)hipFree(arena.base);
-    for (auto& kv : bufs) free_bufs(kv.second);
-    for (auto& kv : tloops) free_tbufs(kv.second.b);
+    for (auto& kv : bufs) release(kv.second);
+    for (auto& kv : tloops) release(kv.second);
     (void)hipEventDestroy(ev_in);
     (void)hipEventDestroy(ev_out);
     (void)hipEventDestroy(ev_fork);
@@ -1590,76 +1571,71 @@ class EngineT : public Engine {
     arena.cap = bytes;
     if (poison()) HIP_OK(hipMemset(arena.base, 0xFF, bytes));
   }
+  // Device buffers of one cached loop shape. Every dalloc registers its pointer with the struct it
+  // allocates for, and release() walks that list: no field is named twice.
   struct Bufs {
     float *xs = nullptr, *mus = nullptr, *tcs = nullptr, *ics = nullptr, *ss = nullptr,
           *cc = nullptr, *sin = nullptr;
     float* noise = nullptr;       // owned copy of injected noise [nT,B,3,H,W] (lazily allocated)
     void* out = nullptr;
-    uint64_t* seed = nullptr;
+    uint64_t* seed = nullptr;     // [seed, element offset of image 0]
     int ldo = 0;
+    std::vector<void*> owned;
   };
-  std::map<std::tuple<int, int, int, int>, Bufs> bufs;    // (B, H, W, nT)
-  void free_bufs(Bufs& b) {
-    for (void* p : {(void*)b.xs, (void*)b.mus, (void*)b.tcs, (void*)b.ics, (void*)b.ss,
-                    (void*)b.cc, (void*)b.sin, (void*)b.noise, b.out, (void*)b.seed})
-      if (p) (void)hipFree(p);
-  }
-  // DAC_POISON=1: fill fresh workspace with 0xFF bytes (NaN in f32/bf16) so any
-  // read-before-write shows up as a NaN in the outputs (debug aid).
-  static bool poison() {
-    static const bool p = getenv("DAC_POISON") && getenv("DAC_POISON")[0] == '1';
-    return p;
-  }
-  template <class X> X* dalloc(size_t n) {
-    void* p = nullptr;
+  template <class X> X* dalloc(Bufs& o, size_t n) {
     const size_t bytes = std::max<size_t>(n * sizeof(X), 16);
-    HIP_OK(hipMalloc(&p, bytes));
-    if (poison()) HIP_OK(hipMemset(p, 0xFF, bytes));
-    return (X*)p;
+    o.owned.push_back(nullptr);
+    HIP_OK(hipMalloc(&o.owned.back(), bytes));
+    if (poison()) HIP_OK(hipMemset(o.owned.back(), 0xFF, bytes));
+    return (X*)o.owned.back();
   }
-  // Loop buffers per shape. Graphs bake these addresses in, so the shape cache is bounded
-  // by dropping every graph together with the buffers when it grows past kMaxShapes.
-  static constexpr size_t kMaxShapes = 8;
-  Bufs& get_bufs(int B, int H, int W, int nT) {
-    auto key = std::make_tuple(B, H, W, nT);
-    auto it = bufs.find(key);
-    if (it != bufs.end()) return it->second;
-    if (bufs.size() >= kMaxShapes) {
+  void release(Bufs& b) {
+    for (void* p : b.owned) (void)hipFree(p);
+    b.owned.clear();
+  }
+  // The fields both loops share: B images of n floats in all, nT steps, a UNet output of out_px
+  // padded pixels.
+  void alloc_loop(Bufs& b, int B, size_t n, int nT, size_t out_px) {
+    b.xs = dalloc<float>(b, n);
+    b.mus = dalloc<float>(b, n);
+    b.tcs = dalloc<float>(b, (size_t)B * std::max(1, unet->ctx));
+    b.ics = dalloc<float>(b, (size_t)B * std::max(1, unet->ctx));
+    b.ss = dalloc<float>(b, (size_t)nT * B * unet->ss_total);
+    b.cc = dalloc<float>(b, (size_t)B * std::max(1, unet->cc_total));
+    b.sin = dalloc<float>(b, (size_t)nT * B * unet->nf);
+    b.ldo = 4;
+    b.out = dalloc<char>(b, out_px * b.ldo * sizeof(T));
+    b.seed = dalloc<uint64_t>(b, 2);
+  }
+  // The entry of a shape cache, filled by fill(entry) on a miss. Graphs bake the buffers' addresses
+  // in, so a cache that is full (max entries) drops every graph together with all its buffers. A
+  // fill that throws releases what the entry holds and leaves no entry.
+  template <class M, class F>
+  typename M::mapped_type& cache_entry(M& m, const typename M::key_type& key, size_t max, F&& fill) {
+    auto it = m.find(key);
+    if (it != m.end()) return it->second;
+    if (m.size() >= max) {
       HIP_OK(hipDeviceSynchronize());
       clear_graphs();
-      for (auto& kv : bufs) free_bufs(kv.second);
-      bufs.clear();
+      for (auto& kv : m) release(kv.second);
+      m.clear();
     }
-    Bufs b;
-    const size_t n = (size_t)B * 3 * H * W;
-    const int Hp = unet->pad_of(H), Wp = unet->pad_of(W);
-    b.xs = dalloc<float>(n);
-    b.mus = dalloc<float>(n);
-    b.tcs = dalloc<float>((size_t)B * std::max(1, unet->ctx));
-    b.ics = dalloc<float>((size_t)B * std::max(1, unet->ctx));
-    b.ss = dalloc<float>((size_t)nT * B * unet->ss_total);
-    b.cc = dalloc<float>((size_t)B * std::max(1, unet->cc_total));
-    b.sin = dalloc<float>((size_t)nT * B * unet->nf);
-    b.ldo = 4;
-    b.out = dalloc<char>((size_t)B * Hp * Wp * b.ldo * sizeof(T));
-    b.seed = dalloc<uint64_t>(2);     // [seed, element offset of image 0]
-    return bufs.emplace(key, b).first->second;
+    auto& e = m[key];
+    try {
+      fill(e);
+    } catch (...) {
+      release(e);
+      m.erase(key);
+      throw;
+    }
+    return e;
   }
-  // Dry run of the same launch sequence: arena size (and argument checks, e.g. the
-  // self-attention fallback) before anything is launched or captured.
-  size_t plan_unet(int B, int H, int W, int nT, bool has_ic) {
-    Arena a;
-    a.dry = true;
-    Run r;
-    r.dry = true;
-    r.ar = &a;
-    set_side(r);       // same allocation sequence as the live (split) forward
-    const float* dummy = (const float*)1;
-    unet->tables(r, nullptr, nT, 0.0, 0.0, 1.0, dummy, has_ic ? dummy : nullptr, B, nullptr, nullptr);
-    const size_t t = a.peak;
-    a.reset();
-    unet->forward(r, nullptr, nullptr, B, H, W, nullptr, has_ic ? dummy : nullptr, nullptr, 4);
-    return std::max(t, a.peak) + (1 << 20);
+  std::map<std::tuple<int, int, int, int>, Bufs> bufs;    // (B, H, W, nT)
+  static constexpr size_t kMaxShapes = 8;
+  Bufs& get_bufs(int B, int H, int W, int nT) {
+    return cache_entry(bufs, std::make_tuple(B, H, W, nT), kMaxShapes, [&](Bufs& b) {
+      alloc_loop(b, B, (size_t)B * 3 * H * W, nT, (size_t)B * unet->pad_of(H) * unet->pad_of(W));
+    });
   }
   void set_side(Run& r) {
     for (int k = 0; k < Run::kSide; ++k) { r.side[k] = side[k]; r.evj[k] = ev_join[k]; }
@@ -1675,15 +1651,41 @@ class EngineT : public Engine {
     set_side(r);
     return r;
   }
+  // A dry Run over `a`: the same launch sequence with nothing launched, for arena sizes, argument
+  // checks, FLOP counts and the profiler's slot counts. sides: fork the split section as the live
+  // recording does (same allocation sequence).
+  Run dry(Arena& a, bool sides = false, Profiler* p = nullptr, const void* zero = nullptr) {
+    Run r;
+    r.dry = true;
+    r.ar = &a;
+    r.prof = p;
+    r.zero = zero;
+    if (sides) set_side(r);
+    return r;
+  }
+  // Arena bytes of a UNet call or loop: dry runs of the tables for (B, nT, has_ic) and of one
+  // forward per listed (images, h, w), the arena reset before each (they also carry the argument
+  // checks, e.g. the self-attention fallback, before anything is launched or captured).
+  struct Fwd { int nb, h, w; };
+  size_t plan(int B, int nT, bool has_ic, std::initializer_list<Fwd> fwds) {
+    Arena a;
+    Run r = dry(a, true);
+    const float* dummy = (const float*)1;
+    unet->tables(r, nullptr, nT, 0.0, 0.0, 1.0, dummy, has_ic ? dummy : nullptr, B, nullptr, nullptr);
+    for (const Fwd& f : fwds) {
+      if (f.nb < 1) continue;
+      a.reset();
+      unet->forward(r, nullptr, nullptr, f.nb, f.h, f.w, nullptr, has_ic ? dummy : nullptr, nullptr, 4);
+    }
+    return a.peak + (1 << 20);
+  }
 
   // ------------------------------------------------------------------ encode
   void encode(const float* img, int B, float* ic, float* dc, hipStream_t st) override {
     need(vit != nullptr, "handle has no vision towers");
     HIP_OK(hipSetDevice(dev));
     Arena a;
-    Run d;
-    d.dry = true;
-    d.ar = &a;
+    Run d = dry(a);
     vit->encode(d, nullptr, B, nullptr, nullptr, dc != nullptr);
     ensure_arena(a.peak + (1 << 20));
     Run r = live(st);
@@ -1697,9 +1699,7 @@ class EngineT : public Engine {
     need(vit != nullptr && cfg.text, "handle has no text tower");
     HIP_OK(hipSetDevice(dev));
     Arena a;
-    Run d;
-    d.dry = true;
-    d.ar = &a;
+    Run d = dry(a);
     vit->encode_text(d, nullptr, N, nullptr);
     ensure_arena(a.peak + (1 << 20));
     Run r = live(st);
@@ -1715,7 +1715,7 @@ class EngineT : public Engine {
     HIP_OK(hipSetDevice(dev));
     const float* tcu = unet->degra ? tc : nullptr;
     const float* icu = unet->imgctx ? icx : nullptr;
-    ensure_arena(plan_unet(B, H, W, 1, icu != nullptr));
+    ensure_arena(plan(B, 1, icu != nullptr, {{B, H, W}}));
     Bufs& b = get_bufs(B, H, W, 1);
     Run r = live(st);
     arena.reset();
@@ -1758,70 +1758,106 @@ class EngineT : public Engine {
       kv.second.graphs.clear();
     }
   }
-  void record_loop(Run& r, Bufs& b, int mode, int B, int H, int W, int nT, bool has_noise,
-                   bool has_tc, bool has_ic) {
+  // One loop call: its arguments and what both entry points derive from them (n = B*3*H*W floats;
+  // mkey = mode | feature bits).
+  struct LoopCall {
+    int mode; float* x; const float *mu, *tc, *icx; int B, H, W, nT; const float* noise; uint64_t seed;
+    hipStream_t st;
+    bool has_tc, has_ic, has_noise; int mkey; size_t n;
+  };
+  LoopCall loop_call(int mode, float* x, const float* mu, const float* tc, const float* icx, int B, int H, int W,
+                     int nT, const float* noise, uint64_t seed, hipStream_t st, int tpf = 1) {
+    need(unet != nullptr, "handle has no UNet");
+    need(tpf >= 1, "tiles_per_forward must be >= 1");
+    need(sched.T > 0, "call dac_sde_schedule first");
+    need(nT >= 1 && nT <= sched.T, "T exceeds the schedule length");
+    LoopCall c{mode, x, mu, tc, icx, B, H, W, nT, noise, seed, st};
+    c.has_tc = tc != nullptr && unet->degra;
+    c.has_ic = icx != nullptr && unet->imgctx;
+    c.has_noise = noise != nullptr;
+    c.mkey = mode | (c.has_tc ? 0 : 2) | (c.has_ic ? 0 : 4) | (c.has_noise ? 8 : 0);
+    c.n = (size_t)B * 3 * H * W;
+    return c;
+  }
+  // Prologue of a loop call: the caller's stream hands over to the private one, which copies the
+  // inputs into the loop's buffers and writes the noise key.
+  void stage(Bufs& b, const LoopCall& c) {
+    if (c.has_noise && !b.noise) b.noise = dalloc<float>(b, (size_t)c.nT * c.n);
+    HIP_OK(hipEventRecord(ev_in, c.st));
+    HIP_OK(hipStreamWaitEvent(priv, ev_in, 0));
+    HIP_OK(hipMemcpyAsync(b.xs, c.x, c.n * 4, hipMemcpyDeviceToDevice, priv));
+    HIP_OK(hipMemcpyAsync(b.mus, c.mu, c.n * 4, hipMemcpyDeviceToDevice, priv));
+    if (c.has_tc) HIP_OK(hipMemcpyAsync(b.tcs, c.tc, (size_t)c.B * unet->ctx * 4, hipMemcpyDeviceToDevice, priv));
+    if (c.has_ic) HIP_OK(hipMemcpyAsync(b.ics, c.icx, (size_t)c.B * unet->ctx * 4, hipMemcpyDeviceToDevice, priv));
+    if (c.has_noise) HIP_OK(hipMemcpyAsync(b.noise, c.noise, (size_t)c.nT * c.n * 4, hipMemcpyDeviceToDevice, priv));
+    // Noise key [seed, element offset of image 0], written in stream order by a kernel. Tiled or
+    // not, a pixel's draw depends on the full image alone.
+    set_u64x2(b.seed, c.seed, noise_offset * (uint64_t)(3 * c.H * c.W), priv);
+  }
+  // Epilogue: the state back to the caller, and the caller's stream waits for it.
+  void finish(Bufs& b, const LoopCall& c) {
+    HIP_OK(hipMemcpyAsync(c.x, b.xs, c.n * 4, hipMemcpyDeviceToDevice, priv));
+    HIP_OK(hipEventRecord(ev_out, priv));
+    HIP_OK(hipStreamWaitEvent(c.st, ev_out, 0));
+  }
+  // Captures what rec() enqueues on the private stream (and the side streams it forks) into a
+  // graph. A throwing rec() still ends the capture; its dead graph is destroyed.
+  template <class F> hipGraph_t capture(F&& rec) {
+    hipGraph_t g = nullptr;
+    HIP_OK(hipStreamBeginCapture(priv, hipStreamCaptureModeThreadLocal));
+    try {
+      rec();
+    } catch (...) {
+      hipGraph_t dead = nullptr;
+      (void)hipStreamEndCapture(priv, &dead);
+      if (dead) (void)hipGraphDestroy(dead);
+      throw;
+    }
+    HIP_OK(hipStreamEndCapture(priv, &g));
+    return g;
+  }
+
+  void record_loop(Run& r, Bufs& b, const LoopCall& c) {
+    const int B = c.B, H = c.H, W = c.W, nT = c.nT;
     const int Hp = unet->pad_of(H), Wp = unet->pad_of(W);
     r.ar->reset();
     // Step i runs the model at time (T - i) * sample_scale (sde_utils.py:302).
-    unet->tables(r, b.sin, nT, (double)nT, -1.0, sched.time_scale, has_tc ? b.tcs : nullptr,
-                 has_ic ? b.ics : nullptr, B, b.ss, b.cc);
-    const size_t n = (size_t)B * 3 * H * W;
+    unet->tables(r, b.sin, nT, (double)nT, -1.0, sched.time_scale, c.has_tc ? b.tcs : nullptr,
+                 c.has_ic ? b.ics : nullptr, B, b.ss, b.cc);
     // Unpadded images: each step's sampler update also writes the next step's UNet input rows
     // (same values unet_prep computes from the new x), one launch less per step.
-    const bool fuse_prep = !getenv("DAC_FUSE_PREP") || atoi(getenv("DAC_FUSE_PREP")) != 0;   // per recording
-    const bool fuse = fuse_prep && sde_step_fuses(b.ldo, H, W, Hp, Wp);
+    const bool fuse = fuse_prep_on() && sde_step_fuses(b.ldo, H, W, Hp, Wp);
     for (int i = 0; i < nT; ++i) {
       const int t = nT - i;
       r.ar->reset();
       void* xin = nullptr;
-      unet->forward(r, b.xs, b.mus, B, H, W, b.ss + (size_t)i * B * unet->ss_total, has_ic ? b.cc : nullptr,
+      unet->forward(r, b.xs, b.mus, B, H, W, b.ss + (size_t)i * B * unet->ss_total, c.has_ic ? b.cc : nullptr,
                     b.out, b.ldo, fuse && i > 0, &xin);
       if (!r.dry)
-        sde_step<T>(mode, b.xs, b.mus, b.out, b.ldo, Hp, Wp, has_noise ? b.noise + (size_t)i * n : nullptr,
-                    b.seed, (uint32_t)t, sched.coef(t, mode), B, H, W, r.st, fuse && i + 1 < nT ? xin : nullptr);
+        sde_step<T>(c.mode, b.xs, b.mus, b.out, b.ldo, Hp, Wp, c.has_noise ? b.noise + (size_t)i * c.n : nullptr,
+                    b.seed, (uint32_t)t, sched.coef(t, c.mode), B, H, W, r.st, fuse && i + 1 < nT ? xin : nullptr);
     }
   }
   void sde_reverse(int mode, float* x, const float* mu, const float* tc, const float* icx, int B,
                    int H, int W, int nT, const float* noise, uint64_t seed, hipStream_t st) override {
-    need(unet != nullptr, "handle has no UNet");
-    need(sched.T > 0, "call dac_sde_schedule first");
-    need(nT >= 1 && nT <= sched.T, "T exceeds the schedule length");
+    const LoopCall c = loop_call(mode, x, mu, tc, icx, B, H, W, nT, noise, seed, st);
     HIP_OK(hipSetDevice(dev));
-    const bool has_tc = tc != nullptr && unet->degra;
-    const bool has_ic = icx != nullptr && unet->imgctx;
-    const bool has_noise = noise != nullptr;
-    ensure_arena(plan_unet(B, H, W, nT, has_ic));
+    ensure_arena(plan(B, nT, c.has_ic, {{B, H, W}}));
     Bufs& b = get_bufs(B, H, W, nT);
-    const size_t n = (size_t)B * 3 * H * W;
-    if (has_noise && !b.noise) b.noise = dalloc<float>((size_t)nT * n);
-    HIP_OK(hipEventRecord(ev_in, st));
-    HIP_OK(hipStreamWaitEvent(priv, ev_in, 0));
-    HIP_OK(hipMemcpyAsync(b.xs, x, n * 4, hipMemcpyDeviceToDevice, priv));
-    HIP_OK(hipMemcpyAsync(b.mus, mu, n * 4, hipMemcpyDeviceToDevice, priv));
-    if (has_tc) HIP_OK(hipMemcpyAsync(b.tcs, tc, (size_t)B * unet->ctx * 4, hipMemcpyDeviceToDevice, priv));
-    if (has_ic) HIP_OK(hipMemcpyAsync(b.ics, icx, (size_t)B * unet->ctx * 4, hipMemcpyDeviceToDevice, priv));
-    if (has_noise) HIP_OK(hipMemcpyAsync(b.noise, noise, (size_t)nT * n * 4, hipMemcpyDeviceToDevice, priv));
-    // Noise key [seed, element offset of image 0], written in stream order by a kernel.
-    set_u64x2(b.seed, seed, noise_offset * (uint64_t)(3 * H * W), priv);
-    const int mkey = mode | (has_tc ? 0 : 2) | (has_ic ? 0 : 4) | (has_noise ? 8 : 0);
-    static const bool no_graph = getenv("DAC_NO_GRAPH") && getenv("DAC_NO_GRAPH")[0] == '1';
-    if (no_graph && prof.kernel_id < 0) {
+    stage(b, c);
+    if (no_graph() && prof.kernel_id < 0) {
       Run r = live(priv);
-      record_loop(r, b, mode, B, H, W, nT, has_noise, has_tc, has_ic);
+      record_loop(r, b, c);
     } else if (prof.kernel_id >= 0 && prof.stamps) {
-      profile_graph(b, mode, B, H, W, nT, has_noise, has_tc, has_ic);
+      profile_graph(b, c);
     } else if (prof.kernel_id >= 0) {
       // Profiling replay: HIP cannot report elapsed time between events recorded by graph
       // nodes (hipEventElapsedTime -> invalid handle), so the same launch sequence runs
       // eagerly on the same stream with an event pair around every launch of the class.
       Arena da;
-      Run d;
-      d.dry = true;
-      d.ar = &da;
-      d.prof = &prof;
-      d.zero = zero_page;
+      Run d = dry(da, false, &prof, zero_page);
       prof.begin_pass();
-      record_loop(d, b, mode, B, H, W, nT, has_noise, has_tc, has_ic);
+      record_loop(d, b, c);
       while (prof.ev.size() < 2 * prof.used) {
         hipEvent_t ev;
         HIP_OK(hipEventCreate(&ev));
@@ -1832,23 +1868,13 @@ class EngineT : public Engine {
       // per-launch event pairs time one stream: no side streams (nor in the dry pass above)
       for (int k = 0; k < Run::kSide; ++k) r.side[k] = nullptr;
       prof.begin_pass();
-      record_loop(r, b, mode, B, H, W, nT, has_noise, has_tc, has_ic);
+      record_loop(r, b, c);
     } else {
-      GKey key{mkey, B, H, W, nT};
+      const GKey key{c.mkey, B, H, W, nT};
       auto it = graphs.find(key);
       if (it == graphs.end()) {
         Run r = live(priv);
-        hipGraph_t g;
-        HIP_OK(hipStreamBeginCapture(priv, hipStreamCaptureModeThreadLocal));
-        try {
-          record_loop(r, b, mode, B, H, W, nT, has_noise, has_tc, has_ic);
-        } catch (...) {
-          hipGraph_t dead;
-          (void)hipStreamEndCapture(priv, &dead);
-          if (dead) (void)hipGraphDestroy(dead);
-          throw;
-        }
-        HIP_OK(hipStreamEndCapture(priv, &g));
+        hipGraph_t g = capture([&] { record_loop(r, b, c); });
         hipGraphExec_t ex;
         HIP_OK(hipGraphInstantiate(&ex, g, nullptr, nullptr, 0));
         HIP_OK(hipGraphDestroy(g));
@@ -1856,9 +1882,7 @@ class EngineT : public Engine {
       }
       HIP_OK(hipGraphLaunch(it->second, priv));
     }
-    HIP_OK(hipMemcpyAsync(x, b.xs, n * 4, hipMemcpyDeviceToDevice, priv));
-    HIP_OK(hipEventRecord(ev_out, priv));
-    HIP_OK(hipStreamWaitEvent(st, ev_out, 0));
+    finish(b, c);
   }
 
   // ------------------------------------------------------------------ tiled loop
@@ -1875,9 +1899,7 @@ class EngineT : public Engine {
              std::tie(o.B, o.H, o.W, o.th, o.tw, o.ov, o.C, o.nT, o.ys, o.xs);
     }
   };
-  struct TBufs {
-    float *xs = nullptr, *mus = nullptr, *tcs = nullptr, *ics = nullptr, *ss = nullptr, *cc = nullptr,
-          *sin = nullptr, *noise = nullptr;
+  struct TBufs : Bufs {
     float *xt = nullptr;          // [C, 3, th, tw] tiles of the current state (one chunk)
     float *mut = nullptr;         // [NT, 3, th, tw] tiles of mu, gathered once per call
     float *epst = nullptr;        // [NT, 3, th, tw] per-tile eps
@@ -1885,12 +1907,8 @@ class EngineT : public Engine {
     float *ssc = nullptr;         // [C, ss_total] the chunk's (scale, shift) rows
     float *cct = nullptr;         // [NT, cc_total] cross-attention constants per tile
     int32_t *ysd = nullptr, *xsd = nullptr;
-    void* out = nullptr;
-    uint64_t* seed = nullptr;
-    int ldo = 0;
   };
-  struct TLoop {
-    TBufs b;
+  struct TLoop : TBufs {
     std::map<int, hipGraphExec_t> graphs;     // by mode | feature bits; null = runs eagerly
   };
   std::map<TKey, TLoop> tloops;
@@ -1898,85 +1916,35 @@ class EngineT : public Engine {
   // A captured loop with more nodes than this is not instantiated: the loop is enqueued eagerly
   // on the private stream instead (the same launch sequence, so the same result).
   static constexpr size_t kMaxGraphNodes = 65536;
-  void free_tbufs(TBufs& b) {
-    for (void* p : {(void*)b.xs, (void*)b.mus, (void*)b.tcs, (void*)b.ics, (void*)b.ss, (void*)b.cc,
-                    (void*)b.sin, (void*)b.noise, (void*)b.xt, (void*)b.mut, (void*)b.epst, (void*)b.eps,
-                    (void*)b.ssc, (void*)b.cct, (void*)b.ysd, (void*)b.xsd, b.out, (void*)b.seed})
-      if (p) (void)hipFree(p);
-    b = TBufs();
-  }
   TLoop& get_tloop(const TKey& key) {
-    auto it = tloops.find(key);
-    if (it != tloops.end()) return it->second;
-    if (tloops.size() >= kMaxTiledShapes) {
-      HIP_OK(hipDeviceSynchronize());
-      clear_graphs();
-      for (auto& kv : tloops) free_tbufs(kv.second.b);
-      tloops.clear();
-    }
-    TLoop& L = tloops[key];
-    TBufs& b = L.b;
-    try {
+    return cache_entry(tloops, key, kMaxTiledShapes, [&](TLoop& b) {
       const int ny = (int)key.ys.size(), nx = (int)key.xs.size(), NT = key.B * ny * nx;
       const size_t n = (size_t)key.B * 3 * key.H * key.W, tn = (size_t)3 * key.th * key.tw;
-      const int Hp = unet->pad_of(key.th), Wp = unet->pad_of(key.tw);
-      b.xs = dalloc<float>(n);
-      b.mus = dalloc<float>(n);
-      b.eps = dalloc<float>(n);
-      b.tcs = dalloc<float>((size_t)key.B * std::max(1, unet->ctx));
-      b.ics = dalloc<float>((size_t)key.B * std::max(1, unet->ctx));
-      b.ss = dalloc<float>((size_t)key.nT * key.B * unet->ss_total);
-      b.cc = dalloc<float>((size_t)key.B * std::max(1, unet->cc_total));
-      b.sin = dalloc<float>((size_t)key.nT * key.B * unet->nf);
-      b.xt = dalloc<float>((size_t)key.C * tn);
-      b.mut = dalloc<float>((size_t)NT * tn);
-      b.epst = dalloc<float>((size_t)NT * tn);
-      b.ssc = dalloc<float>((size_t)key.C * unet->ss_total);
-      b.cct = dalloc<float>((size_t)NT * std::max(1, unet->cc_total));
-      b.ldo = 4;
-      b.out = dalloc<char>((size_t)key.C * Hp * Wp * b.ldo * sizeof(T));
-      b.seed = dalloc<uint64_t>(2);
-      b.ysd = dalloc<int32_t>(ny);
-      b.xsd = dalloc<int32_t>(nx);
+      alloc_loop(b, key.B, n, key.nT, (size_t)key.C * unet->pad_of(key.th) * unet->pad_of(key.tw));
+      b.eps = dalloc<float>(b, n);
+      b.xt = dalloc<float>(b, (size_t)key.C * tn);
+      b.mut = dalloc<float>(b, (size_t)NT * tn);
+      b.epst = dalloc<float>(b, (size_t)NT * tn);
+      b.ssc = dalloc<float>(b, (size_t)key.C * unet->ss_total);
+      b.cct = dalloc<float>(b, (size_t)NT * std::max(1, unet->cc_total));
+      b.ysd = dalloc<int32_t>(b, ny);
+      b.xsd = dalloc<int32_t>(b, nx);
       HIP_OK(hipMemcpy(b.ysd, key.ys.data(), ny * sizeof(int32_t), hipMemcpyHostToDevice));
       HIP_OK(hipMemcpy(b.xsd, key.xs.data(), nx * sizeof(int32_t), hipMemcpyHostToDevice));
-    } catch (...) {
-      free_tbufs(b);
-      tloops.erase(key);
-      throw;
-    }
-    return L;
+    });
   }
-  // Arena bytes of the tiled loop: the tables of the B images, one forward of a full chunk and
-  // one of the ragged last chunk (dry runs; they also carry the forward's argument checks).
-  size_t plan_tiled(int B, int C, int rag, int th, int tw, int nT, bool has_ic) {
-    Arena a;
-    a.dry = true;
-    Run r;
-    r.dry = true;
-    r.ar = &a;
-    set_side(r);
-    const float* dummy = (const float*)1;
-    unet->tables(r, nullptr, nT, 0.0, 0.0, 1.0, dummy, has_ic ? dummy : nullptr, B, nullptr, nullptr);
-    for (int nb : {C, rag}) {
-      if (nb < 1) continue;
-      a.reset();
-      unet->forward(r, nullptr, nullptr, nb, th, tw, nullptr, has_ic ? dummy : nullptr, nullptr, 4);
-    }
-    return a.peak + (1 << 20);
-  }
-  void record_tiled(Run& r, TBufs& b, const TKey& k, int mode, bool has_noise, bool has_tc, bool has_ic) {
+  void record_tiled(Run& r, TBufs& b, const TKey& k, const LoopCall& c) {
     const int ny = (int)k.ys.size(), nx = (int)k.xs.size(), per = ny * nx, NT = k.B * per;
     const int Hp = unet->pad_of(k.th), Wp = unet->pad_of(k.tw);
-    const size_t n = (size_t)k.B * 3 * k.H * k.W, tn = (size_t)3 * k.th * k.tw;
+    const size_t tn = (size_t)3 * k.th * k.tw;
     r.ar->reset();
     // Per-image tables (step i runs the model at (T - i) * sample_scale); a chunk's rows are
     // copies of its tiles' images' rows.
-    unet->tables(r, b.sin, k.nT, (double)k.nT, -1.0, sched.time_scale, has_tc ? b.tcs : nullptr,
-                 has_ic ? b.ics : nullptr, k.B, b.ss, b.cc);
+    unet->tables(r, b.sin, k.nT, (double)k.nT, -1.0, sched.time_scale, c.has_tc ? b.tcs : nullptr,
+                 c.has_ic ? b.ics : nullptr, k.B, b.ss, b.cc);
     if (!r.dry) {
       tile_gather(b.mus, b.mut, b.ysd, b.xsd, k.xs.data(), ny, nx, k.H, k.W, k.th, k.tw, 0, NT, r.st);
-      if (has_ic) rows_gather(b.cc, b.cct, NT, unet->cc_total, 0, per, r.st);
+      if (c.has_ic) rows_gather(b.cc, b.cct, NT, unet->cc_total, 0, per, r.st);
     }
     for (int i = 0; i < k.nT; ++i) {
       const int t = k.nT - i;
@@ -1988,82 +1956,50 @@ class EngineT : public Engine {
           rows_gather(b.ss + (size_t)i * k.B * unet->ss_total, b.ssc, nb, unet->ss_total, k0, per, r.st);
         }
         unet->forward(r, b.xt, b.mut + (size_t)k0 * tn, nb, k.th, k.tw, b.ssc,
-                      has_ic ? b.cct + (size_t)k0 * unet->cc_total : nullptr, b.out, b.ldo);
+                      c.has_ic ? b.cct + (size_t)k0 * unet->cc_total : nullptr, b.out, b.ldo);
         if (!r.dry) unet_out<T>(b.out, b.ldo, b.epst + (size_t)k0 * tn, nb, k.th, k.tw, Hp, Wp, r.st);
       }
       if (!r.dry) {
         tile_blend(b.epst, b.eps, b.ysd, b.xsd, k.xs.data(), k.B, ny, nx, k.H, k.W, k.th, k.tw, k.ov, r.st);
         // The flat fp32 sampler update on the full image (eps is NCHW: ld = 0).
-        sde_step<float>(mode, b.xs, b.mus, b.eps, 0, 1, 1, has_noise ? b.noise + (size_t)i * n : nullptr,
-                        b.seed, (uint32_t)t, sched.coef(t, mode), 1, 1, (int)(n / 3), r.st);
+        sde_step<float>(c.mode, b.xs, b.mus, b.eps, 0, 1, 1, c.has_noise ? b.noise + (size_t)i * c.n : nullptr,
+                        b.seed, (uint32_t)t, sched.coef(t, c.mode), 1, 1, (int)(c.n / 3), r.st);
       }
     }
   }
   void sde_reverse_tiled(int mode, float* x, const float* mu, const float* tc, const float* icx, int B,
                          int H, int W, const TileGrid& g, int tpf, int nT, const float* noise,
                          uint64_t seed, hipStream_t st) override {
-    need(unet != nullptr, "handle has no UNet");
-    need(tpf >= 1, "tiles_per_forward must be >= 1");
-    need(sched.T > 0, "call dac_sde_schedule first");
-    need(nT >= 1 && nT <= sched.T, "T exceeds the schedule length");
+    const LoopCall c = loop_call(mode, x, mu, tc, icx, B, H, W, nT, noise, seed, st, tpf);
     if (prof.kernel_id >= 0)
       throw Error(DAC_E_STATE, "the tiled loop has no profiling mode (disable profiling first)");
     HIP_OK(hipSetDevice(dev));
-    const bool has_tc = tc != nullptr && unet->degra;
-    const bool has_ic = icx != nullptr && unet->imgctx;
-    const bool has_noise = noise != nullptr;
     const int NT = B * (int)g.ys.size() * (int)g.xs.size();
     const int C = std::min(tpf, NT);
-    ensure_arena(plan_tiled(B, C, NT % C, g.th, g.tw, nT, has_ic));
+    // One forward of a full chunk and one of the ragged last chunk.
+    ensure_arena(plan(B, nT, c.has_ic, {{C, g.th, g.tw}, {NT % C, g.th, g.tw}}));
     const TKey key{B, H, W, g.th, g.tw, g.ov, C, nT, g.ys, g.xs};
     TLoop& L = get_tloop(key);
-    TBufs& b = L.b;
-    const size_t n = (size_t)B * 3 * H * W;
-    if (has_noise && !b.noise) b.noise = dalloc<float>((size_t)nT * n);
-    HIP_OK(hipEventRecord(ev_in, st));
-    HIP_OK(hipStreamWaitEvent(priv, ev_in, 0));
-    HIP_OK(hipMemcpyAsync(b.xs, x, n * 4, hipMemcpyDeviceToDevice, priv));
-    HIP_OK(hipMemcpyAsync(b.mus, mu, n * 4, hipMemcpyDeviceToDevice, priv));
-    if (has_tc) HIP_OK(hipMemcpyAsync(b.tcs, tc, (size_t)B * unet->ctx * 4, hipMemcpyDeviceToDevice, priv));
-    if (has_ic) HIP_OK(hipMemcpyAsync(b.ics, icx, (size_t)B * unet->ctx * 4, hipMemcpyDeviceToDevice, priv));
-    if (has_noise) HIP_OK(hipMemcpyAsync(b.noise, noise, (size_t)nT * n * 4, hipMemcpyDeviceToDevice, priv));
-    // The noise key of the untiled loop: a pixel's draw depends on the full image alone.
-    set_u64x2(b.seed, seed, noise_offset * (uint64_t)(3 * H * W), priv);
-    const int mkey = mode | (has_tc ? 0 : 2) | (has_ic ? 0 : 4) | (has_noise ? 8 : 0);
-    static const bool no_graph = getenv("DAC_NO_GRAPH") && getenv("DAC_NO_GRAPH")[0] == '1';
-    auto it = L.graphs.find(mkey);
-    if (it == L.graphs.end() && !no_graph) {
+    stage(L, c);
+    auto it = L.graphs.find(c.mkey);
+    if (it == L.graphs.end() && !no_graph()) {
       Run r = live(priv);
-      hipGraph_t gr = nullptr;
-      HIP_OK(hipStreamBeginCapture(priv, hipStreamCaptureModeThreadLocal));
-      try {
-        record_tiled(r, b, key, mode, has_noise, has_tc, has_ic);
-      } catch (...) {
-        hipGraph_t dead = nullptr;
-        (void)hipStreamEndCapture(priv, &dead);
-        if (dead) (void)hipGraphDestroy(dead);
-        throw;
-      }
-      HIP_OK(hipStreamEndCapture(priv, &gr));
+      hipGraph_t gr = capture([&] { record_tiled(r, L, key, c); });
       size_t nn = 0;
       hipError_t e = hipGraphGetNodes(gr, nullptr, &nn);
       hipGraphExec_t ex = nullptr;
-      // DAC_TILED_MAX_NODES: the limit for this call (tests compare the two forms).
-      const char* lim = getenv("DAC_TILED_MAX_NODES");
-      if (e == hipSuccess && nn <= (lim ? (size_t)atoll(lim) : kMaxGraphNodes)) e = hipGraphInstantiate(&ex, gr, nullptr, nullptr, 0);
+      if (e == hipSuccess && nn <= tiled_max_nodes(kMaxGraphNodes)) e = hipGraphInstantiate(&ex, gr, nullptr, nullptr, 0);
       (void)hipGraphDestroy(gr);
       HIP_OK(e);
-      it = L.graphs.emplace(mkey, ex).first;
+      it = L.graphs.emplace(c.mkey, ex).first;
     }
     if (it != L.graphs.end() && it->second) {
       HIP_OK(hipGraphLaunch(it->second, priv));
     } else {
       Run r = live(priv);
-      record_tiled(r, b, key, mode, has_noise, has_tc, has_ic);
+      record_tiled(r, L, key, c);
     }
-    HIP_OK(hipMemcpyAsync(x, b.xs, n * 4, hipMemcpyDeviceToDevice, priv));
-    HIP_OK(hipEventRecord(ev_out, priv));
-    HIP_OK(hipStreamWaitEvent(st, ev_out, 0));
+    finish(L, c);
   }
 
   // Graph-mode profiling (Profiler::stamps): the loop is recorded and captured exactly as the
@@ -2072,17 +2008,11 @@ class EngineT : public Engine {
   // HIP events on the loop's stream, gives every launch's in-graph duration. The kernel symbol
   // of each launch is read back from the captured graph's kernel nodes (the stamp pointer in
   // their argument block names the launch).
-  void profile_graph(Bufs& b, int mode, int B, int H, int W, int nT, bool has_noise, bool has_tc,
-                     bool has_ic) {
+  void profile_graph(Bufs& b, const LoopCall& c) {
     Arena da;
-    Run d;
-    d.dry = true;
-    d.ar = &da;
-    d.prof = &prof;
-    d.zero = zero_page;
-    set_side(d);       // the same branch structure as the live capture
+    Run d = dry(da, true, &prof, zero_page);       // the same branch structure as the live capture
     prof.begin_pass();
-    record_loop(d, b, mode, B, H, W, nT, has_noise, has_tc, has_ic);
+    record_loop(d, b, c);
     const size_t n = prof.used;
     if (n > prof.scap) {
       if (prof.sbuf) HIP_OK(hipFree(prof.sbuf));
@@ -2095,17 +2025,7 @@ class EngineT : public Engine {
     Run r = live(priv);
     r.prof = &prof;
     prof.begin_pass();
-    hipGraph_t g = nullptr;
-    HIP_OK(hipStreamBeginCapture(priv, hipStreamCaptureModeThreadLocal));
-    try {
-      record_loop(r, b, mode, B, H, W, nT, has_noise, has_tc, has_ic);
-    } catch (...) {
-      hipGraph_t dead = nullptr;
-      (void)hipStreamEndCapture(priv, &dead);
-      if (dead) (void)hipGraphDestroy(dead);
-      throw;
-    }
-    HIP_OK(hipStreamEndCapture(priv, &g));
+    hipGraph_t g = capture([&] { record_loop(r, b, c); });
     if (prof.used != n) {
       (void)hipGraphDestroy(g);
       throw Error(DAC_E_STATE, "profile_graph: dry and live recordings differ");
@@ -2188,17 +2108,13 @@ class EngineT : public Engine {
 
   double unet_flops(int B, int H, int W) override {
     Arena a;
-    Run r;
-    r.dry = true;
-    r.ar = &a;
+    Run r = dry(a);
     unet->forward(r, nullptr, nullptr, B, H, W, nullptr, (const float*)1, nullptr, 4);
     return r.flops;
   }
   double encode_flops(int B) override {
     Arena a;
-    Run r;
-    r.dry = true;
-    r.ar = &a;
+    Run r = dry(a);
     vit->encode(r, nullptr, B, nullptr, nullptr, true);
     return r.flops;
   }
@@ -2229,8 +2145,7 @@ std::unique_ptr<Engine> make_engine(int device, int dtype, const dac_config& cfg
   // handles on an fp16 base, B = 16: 30.08 / 29.83 against 29.17 / 29.32 images/s);
   // DAC_FP8_BASE=f16 runs every non-e4m3 layer in IEEE half instead.
   if (dtype == DAC_FP8) {
-    static const bool h = getenv("DAC_FP8_BASE") && !strcmp(getenv("DAC_FP8_BASE"), "f16");
-    if (h) return std::make_unique<EngineT<f16>>(device, cfg, true);
+    if (fp8_base_f16()) return std::make_unique<EngineT<f16>>(device, cfg, true);
     return std::make_unique<EngineT<bf16>>(device, cfg, true);
   }
   if (dtype == DAC_F16) return std::make_unique<EngineT<f16>>(device, cfg);

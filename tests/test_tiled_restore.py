@@ -25,16 +25,20 @@ FP32_BAR = 1e-4
 
 
 # ----------------------------------------------------------------------------- helpers
+def build_model(unet_sd, dtype):
+    from daclip_amd.unet import ConditionalUNet
+    m = ConditionalUNet(3, 3, 64, [1, 2, 4, 8], 512, True, True, dtype=dtype)
+    m.load_state_dict(unet_sd)
+    return m
+
+
 @pytest.fixture(scope="module")
 def models(unet_sd):
-    from daclip_amd.unet import ConditionalUNet
     cache = {}
 
     def get(dtype):
         if dtype not in cache:
-            m = ConditionalUNet(3, 3, 64, [1, 2, 4, 8], 512, True, True, dtype=dtype)
-            m.load_state_dict(unet_sd)
-            cache[dtype] = m
+            cache[dtype] = build_model(unet_sd, dtype)
         return cache[dtype]
     return get
 
@@ -331,3 +335,56 @@ def test_evaluate_tiled(tmp_path):
     assert res["summary"]["images"] == 2
     for i in range(2):
         assert Image.open(tmp_path / "out" / f"img{i}.png").size == (48, 40)
+
+
+# ----------------------------------------------------------------------------- 10: shape-cache eviction
+# The engine keeps the loop buffers and captured graphs of at most 8 untiled shapes (kMaxShapes)
+# and 4 tiled keys (kMaxTiledShapes); one more drops every buffer and graph of that kind. Each
+# test takes a handle of its own (the same model as `models`), so the cache starts empty and the
+# last new key is the one that evicts. T = 100 cosine schedule, 2 steps, explicit noises.
+EVICT_STEPS = 2
+
+
+def test_untiled_shape_cache_eviction(unet_sd):
+    sde = make_sde(build_model(unet_sd, "fp16"))
+    shapes = [(H, W) for H in (16, 32, 64) for W in (16, 32, 64)]
+
+    def restore(H, W):
+        x, mu, z, tc, ic = inputs(1, H, W, seed=3)
+        sde.set_mu(mu)
+        out = sde.reverse_posterior(x, T=EVICT_STEPS, noises=z[:EVICT_STEPS], text_context=tc, image_context=ic)
+        torch.cuda.synchronize()
+        assert out.shape == x.shape and torch.isfinite(out).all(), (H, W)
+        return out
+    first = [restore(H, W) for H, W in shapes]      # the ninth (B, H, W, T) key evicts the other eight
+    assert torch.equal(restore(*shapes[0]), first[0])            # rebuilt after the eviction
+    assert torch.equal(restore(*shapes[-1]), first[-1])          # the graph captured right after it, replayed
+
+
+def test_tiled_shape_cache_eviction(unet_sd):
+    from daclip_amd import _lib
+    m = build_model(unet_sd, "fp16")
+    sde = make_sde(m)
+    h, L = m._h, _lib.lib()
+    H = W = 48
+    x0, mu, z, tc, ic = inputs(1, H, W, seed=4)
+    z = z[:EVICT_STEPS].contiguous()
+    I32 = ctypes.c_int32
+    ys = [0, 16]
+    grids = [[0, 16], [0, 8, 16], [0, 4, 16], [0, 12, 16], [0, 8, 12, 16]]      # five TKeys
+
+    def restore(xs):
+        x = x0.clone()
+        with torch.cuda.device(m.device):
+            sde._sync_schedule(h)
+            h.check(L.dac_sde_set_time_scale(h.h, float(sde.sample_scale)), "time_scale")
+            h.check(L.dac_set_noise_offset(h.h, 0), "noise_offset")
+            h.check(L.dac_sde_reverse_tiled(h.h, _lib.DAC_POSTERIOR, _lib._ptr(x), _lib._ptr(mu), _lib._ptr(tc),
+                                            _lib._ptr(ic), 1, H, W, 32, 32, 16, (I32 * len(ys))(*ys), len(ys),
+                                            (I32 * len(xs))(*xs), len(xs), 16, EVICT_STEPS, _lib._ptr(z), 1,
+                                            h.stream()), "sde_reverse_tiled")
+        torch.cuda.synchronize()
+        assert torch.isfinite(x).all() and not torch.equal(x, x0), xs
+        return x
+    first = [restore(xs) for xs in grids]           # the fifth key evicts the other four
+    assert torch.equal(restore(grids[0]), first[0])
