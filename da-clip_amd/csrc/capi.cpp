@@ -451,13 +451,32 @@ bool conv_op_args(const dac_conv_desc& d, const void* x1, const void* x2, const 
 
 }  // namespace
 
-int dac_op_conv(const dac_conv_desc* d, const void* x1, const void* x2, const void* w, const float* bias,
-                const float* ss, const void* res1, const void* res2, const float* bbias, const void* w_gs,
-                const float* b_gs, void* y, int* plan_out, void* stream) {
+namespace {
+
+// dac_op_conv / dac_op_conv_ex: e (may be null), w2 and y2 are the extension.
+int conv_op(const dac_conv_desc* d, const dac_conv_ext* e, const void* x1, const void* x2, const void* w,
+            const float* bias, const float* ss, const void* res1, const void* res2, const float* bbias,
+            const void* w_gs, const float* b_gs, void* y, const void* w2, void* y2, int* plan_out, void* stream) {
   if (!d) return DAC_E_ARG;
+  const int uph = e ? e->uph : 0;
+  if (uph < 0 || uph > 2 || (!w2) != (!y2) || (y2 && !e)) return DAC_E_ARG;
+  // The phase layouts keep [rows][taps][Cin] with 12 / 16 (row set, tap) pairs instead of 9.
+  dac_conv_desc dd = *d;
+  if (uph) {
+    if (d->kh != 3 || d->up != 1 || d->cwrap || d->ksplit > 1 || d->Cin < 1 || d->Cin > (1 << 24) ||
+        d->K != (uph == 2 ? 16 : 12) * d->Cin)
+      return DAC_E_ARG;
+    dd.K = 9 * d->Cin;
+  }
   dac::ConvArgs a;
   int stride = 1, pad = 0;
-  if (!conv_op_args(*d, x1, x2, w, bias, ss, res1, res2, bbias, w_gs, b_gs, a, stride, pad)) return DAC_E_ARG;
+  if (!conv_op_args(dd, x1, x2, w, bias, ss, res1, res2, bbias, w_gs, b_gs, a, stride, pad)) return DAC_E_ARG;
+  a.K = d->K;
+  a.uph = uph;
+  if (y2) {
+    if (e->ldy2 < d->Cout) return DAC_E_ARG;
+    a.w2 = w2; a.y2 = y2; a.ldy2 = e->ldy2;
+  }
   const int es = d->dtype == DAC_F32 ? 4 : 2;
   KnobOverride knobs(*d);
   // Planning never touches HIP (plan-only calls and every refusal stay off the device); a launch
@@ -474,21 +493,68 @@ int dac_op_conv(const dac_conv_desc* d, const void* x1, const void* x2, const vo
   DevBuf zero, part;
   if (!zero.alloc(256)) return DAC_E_NOMEM;
   if (a.ksplit > 1 && !part.alloc((size_t)a.ksplit * a.B * a.Ho * a.Wo * a.Cout * sizeof(float))) return DAC_E_NOMEM;
-  hipError_t e = hipMemsetAsync(zero.p, 0, 256, st);
+  hipError_t err = hipMemsetAsync(zero.p, 0, 256, st);
   a.y = y; a.zero = zero.p; a.part = (float*)part.p;
-  if (e == hipSuccess) {
+  if (err == hipSuccess) {
     try {
       if (d->dtype == DAC_BF16) dac::conv<__bf16>(a, d->kh, d->kh, stride, pad, st);
       else if (d->dtype == DAC_F16) dac::conv<_Float16>(a, d->kh, d->kh, stride, pad, st);
       else dac::conv<float>(a, d->kh, d->kh, stride, pad, st);
-      e = hipGetLastError();
+      err = hipGetLastError();
     } catch (const std::exception&) {
       (void)hipStreamSynchronize(st);
       return DAC_E_ARG;
     }
   }
   const hipError_t es2 = hipStreamSynchronize(st);
-  return e == hipSuccess && es2 == hipSuccess ? DAC_OK : DAC_E_HIP;
+  return err == hipSuccess && es2 == hipSuccess ? DAC_OK : DAC_E_HIP;
+}
+
+}  // namespace
+
+int dac_op_conv(const dac_conv_desc* d, const void* x1, const void* x2, const void* w, const float* bias,
+                const float* ss, const void* res1, const void* res2, const float* bbias, const void* w_gs,
+                const float* b_gs, void* y, int* plan_out, void* stream) {
+  return conv_op(d, nullptr, x1, x2, w, bias, ss, res1, res2, bbias, w_gs, b_gs, y, nullptr, nullptr, plan_out, stream);
+}
+
+int dac_op_conv_ex(const dac_conv_desc* d, const dac_conv_ext* e, const void* x1, const void* x2, const void* w,
+                   const float* bias, const float* ss, const void* res1, const void* res2, const float* bbias,
+                   const void* w_gs, const float* b_gs, void* y, const void* w2, void* y2, int* plan_out,
+                   void* stream) {
+  return conv_op(d, e, x1, x2, w, bias, ss, res1, res2, bbias, w_gs, b_gs, y, w2, y2, plan_out, stream);
+}
+
+int dac_op_rbfuse(const dac_rb_desc* d, const void* x1, const void* x2, const void* w1, const void* w2,
+                  const void* wr, const float* ss, void* y, int* geom_out, void* stream) {
+  if (!d || !x1 || !w1 || !w2 || !ss || ((uintptr_t)ss & 15)) return DAC_E_ARG;
+  if (d->dtype != DAC_BF16 && d->dtype != DAC_F16) return DAC_E_ARG;
+  const int LIM = 1 << 24;
+  if (d->B < 1 || d->H < 1 || d->W < 1 || d->C1 < 1 || d->Cin < 1 || d->B > LIM || d->H > LIM || d->W > LIM ||
+      d->C1 > LIM || d->Cin > LIM || (long)d->B * d->H * d->W > ((long)1 << 30))
+    return DAC_E_ARG;
+  if (d->C1 < d->Cin && (!x2 || d->ld2 < d->Cin - d->C1)) return DAC_E_ARG;
+  if (d->ld1 < (d->C1 < d->Cin ? d->C1 : d->Cin) || d->ldy < 64 || d->ss_ld < 0) return DAC_E_ARG;
+  dac::RbArgs a{};
+  a.x1 = x1; a.x2 = x2; a.ld1 = d->ld1; a.ld2 = d->ld2; a.C1 = d->C1; a.Cin = d->Cin;
+  a.B = d->B; a.H = d->H; a.W = d->W; a.w1 = w1; a.w2 = w2; a.wr = wr; a.ss = ss; a.ss_ld = d->ss_ld;
+  a.y = y; a.ldy = d->ldy;
+  const bool served = dac::rbfuse_ok(a);
+  if (served && geom_out) dac::rbfuse_geometry(a, geom_out[0], geom_out[1]);
+  if (!y) return served ? 1 : 0;
+  if (!served) return DAC_E_ARG;
+  const hipStream_t st = (hipStream_t)stream;
+  hipError_t err = hipSuccess;
+  try {
+    if (d->dtype == DAC_BF16) dac::rbfuse<__bf16>(a, st);
+    else dac::rbfuse<_Float16>(a, st);
+    err = hipGetLastError();
+  } catch (const std::exception&) {
+    (void)hipStreamSynchronize(st);
+    return DAC_E_ARG;
+  }
+  const hipError_t es2 = hipStreamSynchronize(st);
+  return err == hipSuccess && es2 == hipSuccess ? DAC_OK : DAC_E_HIP;
 }
 
 namespace {

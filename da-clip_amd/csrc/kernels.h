@@ -159,6 +159,9 @@ struct RbArgs {
 };
 bool rbfuse_pays(const RbArgs& a);
 bool rbfuse_ok(const RbArgs& a);
+// The launch geometry rbfuse() uses for arguments rbfuse_ok accepts: band height (output rows per
+// block) and strip width (output columns per block).
+void rbfuse_geometry(const RbArgs& a, int& rb, int& sw);
 template <typename T>
 void rbfuse(const RbArgs& a, hipStream_t st);
 // Register-stationary 3x3 conv, 64 -> 64 (conv3r.hip, 16-bit types): the shapes it serves

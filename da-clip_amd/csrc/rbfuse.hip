@@ -516,16 +516,19 @@ static int rbfuse_rb(const RbArgs& a, int SW) {
   return rb;
 }
 
+void rbfuse_geometry(const RbArgs& a, int& rb, int& sw) {
+  sw = a.Cin == 64 ? RBF<64>::SW : RBF<128>::SW;
+  rb = rbfuse_rb(a, sw);
+}
+
 template <typename T>
 void rbfuse(const RbArgs& a, hipStream_t st) {
   if (!rbfuse_ok(a)) throw std::invalid_argument("rbfuse: arguments rejected by rbfuse_ok");
-  if (a.Cin == 64) {
-    const int rb = rbfuse_rb(a, RBF<64>::SW);
-    rbfuse_kernel<T, 64><<<a.B * (a.H / rb) * (a.W / RBF<64>::SW), 512, 0, st>>>(a, rb);
-  } else {
-    const int rb = rbfuse_rb(a, RBF<128>::SW);
-    rbfuse_kernel<T, 128><<<a.B * (a.H / rb) * (a.W / RBF<128>::SW), 512, 0, st>>>(a, rb);
-  }
+  int rb, sw;
+  rbfuse_geometry(a, rb, sw);
+  const int nb = a.B * (a.H / rb) * (a.W / sw);
+  if (a.Cin == 64) rbfuse_kernel<T, 64><<<nb, 512, 0, st>>>(a, rb);
+  else rbfuse_kernel<T, 128><<<nb, 512, 0, st>>>(a, rb);
 }
 template void rbfuse<bf16>(const RbArgs&, hipStream_t);
 template void rbfuse<f16>(const RbArgs&, hipStream_t);

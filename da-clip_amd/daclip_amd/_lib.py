@@ -40,7 +40,7 @@ EXPORTS = ["dac_create", "dac_destroy", "dac_set_weight", "dac_finalize_weights"
            "dac_profile_read", "dac_profile_mode", "dac_profile_launch", "dac_profile_graph_ms",
            "dac_op_attention", "dac_image_metrics_workspace", "dac_image_metrics", "dac_last_error",
            "dac_sde_reverse_tiled", "dac_op_tile_blend", "dac_op_linear_attention",
-           "dac_op_linear_attention_weff", "dac_op_conv", "dac_op_pack"]
+           "dac_op_linear_attention_weff", "dac_op_conv", "dac_op_pack", "dac_op_conv_ex", "dac_op_rbfuse"]
 DAC_CONV_KEEP, DAC_CONV_PLAN_N = -1000, 8
 # enum dac_pack_layout
 (DAC_PACK_CODEC, DAC_PACK_EMU_FP16, DAC_PACK_CONV, DAC_PACK_DUAL, DAC_PACK_UPH_ROW, DAC_PACK_UPH_COL, DAC_PACK_Q8C3,
@@ -66,6 +66,16 @@ class DacConvDesc(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int) for n in (
         "dtype", "kh", "B", "Hs", "Ws", "up", "C1", "Cin", "ld1", "ld2", "Cout", "K", "ldy", "act", "cwrap",
         "ksplit", "ss_ld", "ldr1", "ldr2", "bb_ld", "conv3_force", "conv2_force", "conv2_force32")]
+
+
+class DacConvExt(ctypes.Structure):
+    """dac_conv_ext (include/daclip_hip.h): the phase form and the second output's pitch for dac_op_conv_ex."""
+    _fields_ = [(n, ctypes.c_int) for n in ("uph", "ldy2")]
+
+
+class DacRbDesc(ctypes.Structure):
+    """dac_rb_desc (include/daclip_hip.h): one fused-ResBlock launch for dac_op_rbfuse."""
+    _fields_ = [(n, ctypes.c_int) for n in ("dtype", "B", "H", "W", "C1", "Cin", "ld1", "ld2", "ss_ld", "ldy")]
 
 
 class DacPackDesc(ctypes.Structure):
@@ -117,6 +127,9 @@ def lib() -> ctypes.CDLL:
         "dac_op_linear_attention": (I, [P, P, P, P, P, P, I, I, I, I, F, P]),
         "dac_op_linear_attention_weff": (I, [P, P, P, I, I, I, I, F, P]),
         "dac_op_conv": (I, [ctypes.POINTER(DacConvDesc), P, P, P, P, P, P, P, P, P, P, P, ctypes.POINTER(I), P]),
+        "dac_op_conv_ex": (I, [ctypes.POINTER(DacConvDesc), ctypes.POINTER(DacConvExt), P, P, P, P, P, P, P, P, P, P, P, P, P,
+                               ctypes.POINTER(I), P]),
+        "dac_op_rbfuse": (I, [ctypes.POINTER(DacRbDesc), P, P, P, P, P, P, P, ctypes.POINTER(I), P]),
         "dac_op_pack": (I, [ctypes.POINTER(DacPackDesc), P, P, P, P, ctypes.POINTER(P), ctypes.POINTER(ctypes.c_size_t),
                             ctypes.POINTER(ctypes.c_size_t)]),
         "dac_image_metrics_workspace": (ctypes.c_size_t, [I, I, I, I, I]),

@@ -300,6 +300,65 @@ int dac_op_conv(const dac_conv_desc* d, const void* x1, const void* x2, const vo
                 const float* ss, const void* res1, const void* res2, const float* bbias, const void* w_gs,
                 const float* b_gs, void* y, int* plan_out, void* stream);
 
+/* Op-level test hook: dac_op_conv with the two ConvArgs features only the stride-1 3x3 kernels
+ * have. Everything dac_op_conv documents holds unchanged (operands, plan-only mode with
+ * y == NULL, plan_out, the knob override and its restore, the hook-owned zero page and split-K
+ * workspace, stream synchronisation, scratch freed on every path); e == NULL is dac_op_conv.
+ *   Fused second output (the ResBlock's 1x1 res_conv, csrc/kernels.h ConvArgs::w2 / y2):
+ *     y2[m, n] = sum_c x[m, c] w2[n, c] over the same (x1 | x2) input at the centre tap, no
+ *     epilogue; w2 is [Cout][Cin] and y2 has row pitch e->ldy2, both in `dtype`. Served by conv3r
+ *     (Cin 128) and the 16-bit C3I_RES v4 tiles, with the built-in selection (conv3_force < 0).
+ *   e->uph in {0, 1, 2}: the row- (1) or row+column-phase (2) form of an up = 1 conv
+ *     (ConvArgs::uph). w is then the DAC_PACK_UPH_ROW layout [Cout][4][3][Cin] (d->K = 12 Cin) or
+ *     the DAC_PACK_UPH_COL layout [Cout][4][4][Cin] (d->K = 16 Cin) that dac_op_pack produces:
+ *     output row 2i + a reads source rows i - 1 + a + s (s = 0, 1) with weight row set 2a + s;
+ *     uph = 1 keeps the three column taps over the upsampled columns, uph = 2 folds them the same
+ *     way (output column 2j + b reads source columns j - 1 + b + t with column set 2b + t).
+ * In plan-only mode y2 is only tested for null, like every other pointer.
+ * DAC_E_ARG, before any device work, for everything dac_op_conv refuses and: exactly one of w2 /
+ * y2; w2 / y2 without e, or with e->ldy2 < Cout; uph outside {0, 1, 2}; uph without up = 1 (or kh
+ * != 3); d->K not the uph layout's (12 Cin / 16 Cin; 9 Cin with uph = 0); uph together with
+ * cwrap or ksplit; and any combination the selection answers with kind 0 (a fused output or a
+ * phase form on a shape, dtype or forced configuration that has no such kernel). */
+typedef struct dac_conv_ext {
+  int uph;
+  int ldy2;
+} dac_conv_ext;
+int dac_op_conv_ex(const dac_conv_desc* d, const dac_conv_ext* e, const void* x1, const void* x2, const void* w,
+                   const float* bias, const float* ss, const void* res1, const void* res2, const float* bbias,
+                   const void* w_gs, const float* b_gs, void* y, const void* w2, void* y2, int* plan_out,
+                   void* stream);
+
+/* Op-level test hook: the fused ResBlock kernel (csrc/rbfuse.hip, csrc/kernels.h RbArgs) as ONE
+ * launch, handle-less: the caller owns every tensor, all on the current device.
+ *   h = SiLU(conv3x3(x, w1) * (1 + scale) + shift),  y = SiLU(conv3x3(h, w2)) + res,
+ *   res = x (Cin = 64) or x wr^T (Cin = 128); both convs zero-pad, h is zero outside the image.
+ * x = (x1 | x2): channels [0, C1) from x1 (row pitch ld1), [C1, Cin) from x2 (ld2), NHWC rows of
+ * B * H * W pixels; w1 [64][3][3][Cin], w2 [64][3][3][64], wr [64][Cin] (Cin = 128) or NULL
+ * (Cin = 64); x, w and y (row pitch ldy, 64 channels) in `dtype` (DAC_BF16 / DAC_F16); ss fp32,
+ * 16-byte aligned: scale [b * ss_ld + n], shift [b * ss_ld + 64 + n].
+ * geom_out (2 ints, or null) receives the launch geometry: band height (output rows per block)
+ * and strip width (output columns per block).
+ * y == NULL: the served-query. Nothing touches the device (pointers are only tested for null /
+ * alignment); returns 1 if rbfuse_ok takes these arguments (geom_out filled), 0 if not.
+ * Otherwise runs on `stream`, synchronises it and returns DAC_OK.
+ * DAC_E_ARG, before any device work: a null descriptor, x1, w1, w2 or ss; ss not 16-byte
+ * aligned; a dtype other than the two 16-bit ones; B, H, W, C1, Cin < 1 (or above 2^24, or
+ * B * H * W above 2^30); C1 < Cin without x2 or with ld2 < Cin - C1; ld1 below the channels read
+ * from x1; ldy < 64; ss_ld < 0; and, with y != NULL, whatever rbfuse_ok refuses (Cin outside
+ * {64, 128}; wr given with Cin = 64 or missing with Cin = 128; W below 256 or not a multiple of
+ * the strip width, 128 columns at Cin 64 and 64 at Cin 128; two sources other than 64 | 64;
+ * pitches that are not multiples of 8 elements; ss_ld not a multiple of 4; an image of 2^31 bytes
+ * or more). */
+typedef struct dac_rb_desc {
+  int dtype;
+  int B, H, W;
+  int C1, Cin, ld1, ld2;
+  int ss_ld, ldy;
+} dac_rb_desc;
+int dac_op_rbfuse(const dac_rb_desc* d, const void* x1, const void* x2, const void* w1, const void* w2,
+                  const void* wr, const float* ss, void* y, int* geom_out, void* stream);
+
 /* Host-only test hook: one weight-packing function of csrc/pack.h, the code dac_finalize_weights
  * packs with, on host arrays. No HIP call, so it works without a GPU. w (and gain / beta / bias
  * where the layout has them) are fp32 as a checkpoint stores them; `dtype` is the storage type

@@ -1,5 +1,7 @@
-"""Op-level numerics of the 3x3 conv kernel family on the GPU (bf16 and IEEE-half storage, fp32
-accumulate).
+"""Numerics of the 3x3 conv kernel family at the UNet's own shapes on the GPU (bf16 and IEEE-half
+storage, fp32 accumulate): the workload-shape complement of the op-level tests in
+tests/test_conv3x3_ops.py, which check one launch at a time through the C ABI against an fp64
+reference at the small and odd shapes where the launchers branch, with bounds from a rounding model.
 
 tools/convbench (built in-tree by __graft_entry__.build) runs every UNet 3x3 shape through each
 kernel choice on random inputs and compares the full output with a naive one-thread-per-output

@@ -1,5 +1,6 @@
-"""Op-level tests of the conv kernels the dispatcher (csrc/conv_plan.cpp) can choose beyond the
-stride-1 3x3 family: the 1x1 GEMM family (conv2_kernel: forced tile configurations, minimal /
+"""Op-level tests of the conv kernels the dispatcher (csrc/conv_plan.cpp) can choose, except the
+stride-1 3x3 family and the fused ResBlock, which tests/test_conv3x3_ops.py covers with this file's
+helpers and method: the 1x1 GEMM family (conv2_kernel: forced tile configurations, minimal /
 general / swapped / GEGLU epilogues, ring depths, partial M and N tiles, two sources), 1x1 and 3x3
 split-K with conv_part_reduce, conv_down (4x4 stride 2), conv7 and conv3n (conv_edge.hip, plain and
 split-precision weights), their generic fallbacks (v2 row-tap 7x7, v2 kh = 4, conv1, the 256x16 v4

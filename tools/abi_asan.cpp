@@ -105,6 +105,74 @@ int main() {
     q = cd; q.kh = 7; q.C1 = q.Cin = q.ld1 = 8; q.K = 896; q.cwrap = 1; q.dtype = DAC_F32;
     EXPECT(call(q, dummy, nullptr, dummy, dummy) == DAC_E_ARG);                                  // row-tap dual in fp32
     q = cd; q.kh = 4; q.Hs = 7; q.K = 16 * 64; EXPECT(call(q, dummy, nullptr, dummy, dummy) == DAC_E_ARG);   // odd input
+    // dac_op_conv_ex: the fused second output and the phase forms; refusals before any device work,
+    // plan-only calls (y == NULL) on valid arguments.
+    dac_conv_desc c3 = cd;
+    c3.kh = 3; c3.Hs = 4; c3.Ws = 256; c3.C1 = c3.Cin = c3.ld1 = 128; c3.Cout = c3.ldy = 64; c3.K = 9 * 128;
+    dac_conv_ext ex = {0, 64};
+    auto callx = [&](const dac_conv_desc& q, const dac_conv_ext* e, const void* w2, void* y2, void* y) {
+      return dac_op_conv_ex(&q, e, dummy, nullptr, dummy, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                            y, w2, y2, plan, nullptr);
+    };
+    EXPECT(dac_op_conv_ex(nullptr, &ex, dummy, nullptr, dummy, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                          nullptr, dummy, nullptr, nullptr, plan, nullptr) == DAC_E_ARG);
+    EXPECT(callx(c3, nullptr, nullptr, nullptr, nullptr) == DAC_OK && plan[0] == 4);      // e == NULL: dac_op_conv (conv3r)
+    EXPECT(callx(c3, &ex, dummy, dummy, nullptr) == DAC_OK && plan[0] == 4);              // conv3r with y2
+    EXPECT(callx(c3, &ex, nullptr, dummy, dummy) == DAC_E_ARG);                           // y2 without w2
+    EXPECT(callx(c3, &ex, dummy, nullptr, dummy) == DAC_E_ARG);                           // w2 without y2
+    EXPECT(callx(c3, nullptr, dummy, dummy, dummy) == DAC_E_ARG);                         // y2 without its pitch
+    ex.ldy2 = 63; EXPECT(callx(c3, &ex, dummy, dummy, dummy) == DAC_E_ARG);               // ldy2 < Cout
+    ex.ldy2 = 64;
+    q = c3; q.conv3_force = 0; EXPECT(callx(q, &ex, dummy, dummy, dummy) == DAC_E_ARG);   // v3 fuses nothing
+    q = c3; q.dtype = DAC_F32; EXPECT(callx(q, &ex, dummy, dummy, dummy) == DAC_E_ARG);   // 16-bit only
+    q = c3; q.kh = 1; q.K = 128; EXPECT(callx(q, &ex, dummy, dummy, dummy) == DAC_E_ARG); // 3x3 only
+    q = c3; q.Hs = 8; q.Ws = 64; q.C1 = q.Cin = q.ld1 = 64; q.up = 1; q.K = 12 * 64;
+    ex.uph = 1; EXPECT(callx(q, &ex, nullptr, nullptr, nullptr) == DAC_OK && plan[0] == 6 && (plan[5] & 8192));
+    ex.uph = 2; EXPECT(callx(q, &ex, nullptr, nullptr, dummy) == DAC_E_ARG);              // K is the row layout's
+    q.K = 16 * 64; EXPECT(callx(q, &ex, nullptr, nullptr, nullptr) == DAC_OK && (plan[5] & 16384));
+    ex.uph = 3; EXPECT(callx(q, &ex, nullptr, nullptr, dummy) == DAC_E_ARG);
+    ex.uph = -1; EXPECT(callx(q, &ex, nullptr, nullptr, dummy) == DAC_E_ARG);
+    ex.uph = 0; EXPECT(callx(q, &ex, nullptr, nullptr, dummy) == DAC_E_ARG);              // K = 16 Cin without uph
+    ex.uph = 2; q.up = 0; EXPECT(callx(q, &ex, nullptr, nullptr, dummy) == DAC_E_ARG);    // uph without up
+    q.up = 1; q.dtype = DAC_F32; EXPECT(callx(q, &ex, nullptr, nullptr, dummy) == DAC_E_ARG);   // no fp32 phase tile
+    q.dtype = DAC_BF16; q.Ws = 32; EXPECT(callx(q, &ex, nullptr, nullptr, dummy) == DAC_E_ARG); // uph = 2: rows >= 128
+    q.Ws = 64; EXPECT(callx(q, &ex, dummy, dummy, dummy) == DAC_E_ARG);                   // no phase tile fuses y2
+  }
+  // dac_op_rbfuse: the served-query (y == NULL) and the refusals, all before any device work.
+  {
+    alignas(16) static float ssb[4];
+    dac_rb_desc rd = {DAC_BF16, 2, 3, 256, 64, 64, 64, 0, 128, 64};
+    int geom[2] = {0, 0};
+    auto rb = [&](const dac_rb_desc& q, const void* x1, const void* x2, const void* w1, const void* w2, const void* wr,
+                  const float* ss, void* y) { return dac_op_rbfuse(&q, x1, x2, w1, w2, wr, ss, y, geom, nullptr); };
+    EXPECT(rb(rd, dummy, nullptr, dummy, dummy, nullptr, ssb, nullptr) == 1 && geom[0] == 1 && geom[1] == 128);
+    EXPECT(dac_op_rbfuse(nullptr, dummy, nullptr, dummy, dummy, nullptr, ssb, dummy, geom, nullptr) == DAC_E_ARG);
+    EXPECT(rb(rd, nullptr, nullptr, dummy, dummy, nullptr, ssb, dummy) == DAC_E_ARG);
+    EXPECT(rb(rd, dummy, nullptr, nullptr, dummy, nullptr, ssb, dummy) == DAC_E_ARG);
+    EXPECT(rb(rd, dummy, nullptr, dummy, nullptr, nullptr, ssb, dummy) == DAC_E_ARG);
+    EXPECT(rb(rd, dummy, nullptr, dummy, dummy, nullptr, nullptr, dummy) == DAC_E_ARG);
+    EXPECT(rb(rd, dummy, nullptr, dummy, dummy, nullptr, ssb + 1, dummy) == DAC_E_ARG);   // ss alignment
+    EXPECT(rb(rd, dummy, nullptr, dummy, dummy, dummy, ssb, dummy) == DAC_E_ARG);         // wr with Cin 64
+    EXPECT(rb(rd, dummy, nullptr, dummy, dummy, dummy, ssb, nullptr) == 0);               // ... as a query
+    dac_rb_desc q = rd;
+    q.dtype = DAC_F32; EXPECT(rb(q, dummy, nullptr, dummy, dummy, nullptr, ssb, dummy) == DAC_E_ARG);
+    q = rd; q.B = 0; EXPECT(rb(q, dummy, nullptr, dummy, dummy, nullptr, ssb, dummy) == DAC_E_ARG);
+    q = rd; q.H = -1; EXPECT(rb(q, dummy, nullptr, dummy, dummy, nullptr, ssb, dummy) == DAC_E_ARG);
+    q = rd; q.W = 192; EXPECT(rb(q, dummy, nullptr, dummy, dummy, nullptr, ssb, dummy) == DAC_E_ARG);
+    EXPECT(rb(q, dummy, nullptr, dummy, dummy, nullptr, ssb, nullptr) == 0);
+    q = rd; q.W = 320; EXPECT(rb(q, dummy, nullptr, dummy, dummy, nullptr, ssb, dummy) == DAC_E_ARG);   // strips of 128
+    q = rd; q.ldy = 63; EXPECT(rb(q, dummy, nullptr, dummy, dummy, nullptr, ssb, dummy) == DAC_E_ARG);
+    q = rd; q.ldy = 68; EXPECT(rb(q, dummy, nullptr, dummy, dummy, nullptr, ssb, dummy) == DAC_E_ARG);
+    q = rd; q.ld1 = 56; EXPECT(rb(q, dummy, nullptr, dummy, dummy, nullptr, ssb, dummy) == DAC_E_ARG);
+    q = rd; q.ss_ld = -4; EXPECT(rb(q, dummy, nullptr, dummy, dummy, nullptr, ssb, dummy) == DAC_E_ARG);
+    q = rd; q.ss_ld = 130; EXPECT(rb(q, dummy, nullptr, dummy, dummy, nullptr, ssb, dummy) == DAC_E_ARG);
+    q = rd; q.Cin = 128; q.W = 320;
+    EXPECT(rb(q, dummy, nullptr, dummy, dummy, dummy, ssb, dummy) == DAC_E_ARG);          // C1 < Cin, no x2
+    q.ld2 = 56; EXPECT(rb(q, dummy, dummy, dummy, dummy, dummy, ssb, dummy) == DAC_E_ARG);
+    q.ld2 = 96; EXPECT(rb(q, dummy, dummy, dummy, dummy, dummy, ssb, nullptr) == 1 && geom[0] == 1 && geom[1] == 64);
+    EXPECT(rb(q, dummy, dummy, dummy, dummy, nullptr, ssb, dummy) == DAC_E_ARG);          // wr missing at Cin 128
+    q.C1 = 32; q.ld1 = 32; EXPECT(rb(q, dummy, dummy, dummy, dummy, dummy, ssb, dummy) == DAC_E_ARG);   // 32 | 96
+    q = rd; q.Cin = q.C1 = q.ld1 = 96; EXPECT(rb(q, dummy, nullptr, dummy, dummy, nullptr, ssb, dummy) == DAC_E_ARG);
   }
   // dac_op_pack (host only): every layout family writes into heap buffers of exactly the queried
   // sizes, and the refusals come before any buffer is touched.
