@@ -2,10 +2,7 @@
 // Every entry point converts exceptions into a negative DAC_E* code + dac_last_error().
 #include <cstdio>
 #include <algorithm>
-#include <array>
-#include <map>
 #include <cmath>
-#include <set>
 
 #include "engine.h"
 #include "conv_plan.h"
@@ -777,8 +774,7 @@ int dac_image_metrics(const float* out, const float* gt, int B, int C, int H, in
 
 int dac_profile_enable(dac_handle* h, int kernel_id) {
   return guard(h, [&]() -> int {
-    h->eng->prof.kernel_id = kernel_id;
-    h->eng->prof.begin_pass();
+    h->eng->prof.enable(kernel_id);
     return DAC_OK;
   });
 }
@@ -788,42 +784,13 @@ int dac_profile_read(dac_handle* h, double* mean_ms, double* flops_per_launch,
   int n = 0;
   int rc = guard(h, [&]() -> int {
     auto& p = h->eng->prof;
-    if (p.kernel_id < 0 || p.launches == 0) throw dac::Error(DAC_E_STATE, "nothing profiled");
-    double tot = 0;
-    std::map<std::string, std::array<double, 3>> by;   // label -> count, ms, flops
-    if (p.stamps && p.lms.size() != p.launches) throw dac::Error(DAC_E_STATE, "graph profile incomplete");
-    if (!p.stamps) p.lms.assign(p.launches, 0.0);
-    for (size_t i = 0; i < p.launches; ++i) {
-      if (!p.stamps) {
-        HIP_OK(hipEventSynchronize(p.ev[2 * i + 1]));
-        float ms = 0;
-        HIP_OK(hipEventElapsedTime(&ms, p.ev[2 * i], p.ev[2 * i + 1]));
-        p.lms[i] = ms;
-      }
-      const double ms = p.lms[i];
-      tot += ms;
-      if (p.kernel_id == dac::Profiler::ALL && i < p.labels.size()) {
-        auto& v = by[p.labels[i]];
-        v[0] += 1; v[1] += ms; v[2] += p.lflops[i];
-      }
-    }
-    if (!by.empty() && getenv("DAC_PROFILE_PRINT")) {   // per-shape report (kernel_id ALL)
-      std::vector<std::pair<double, std::string>> rows;
-      for (auto& kv : by) {
-        char line[320];
-        snprintf(line, sizeof line, "%6.0f x %8.1f us = %8.2f ms  %7.1f TF/s  %s", kv.second[0],
-                 1e3 * kv.second[1] / kv.second[0], kv.second[1],
-                 kv.second[2] / (kv.second[1] * 1e-3) / 1e12, kv.first.c_str());
-        rows.push_back({kv.second[1], line});
-      }
-      std::sort(rows.rbegin(), rows.rend());
-      fprintf(stderr, "[dac conv profile] %zu launches, %.2f ms total\n", p.launches, tot);
-      for (auto& r : rows) fprintf(stderr, "  %s\n", r.second.c_str());
-    }
-    n = (int)p.launches;
-    if (mean_ms) *mean_ms = tot / n;
-    if (flops_per_launch) *flops_per_launch = p.flops / n;
-    if (bytes_per_launch) *bytes_per_launch = p.bytes / n;
+    if (p.pass == dac::Pass::events) p.finish_events();
+    const auto s = p.summary();
+    if (p.kernel_id == dac::Profiler::ALL && getenv("DAC_PROFILE_PRINT")) p.report(stderr);   // per-shape report
+    n = s.n;
+    if (mean_ms) *mean_ms = s.mean_ms;
+    if (flops_per_launch) *flops_per_launch = s.flops_per_launch;
+    if (bytes_per_launch) *bytes_per_launch = s.bytes_per_launch;
     return DAC_OK;
   });
   return rc < 0 ? rc : n;
@@ -840,17 +807,15 @@ int dac_profile_launch(dac_handle* h, int i, double* ms, double* flops, double* 
                        double* start_ms, int* in_branch, char* label, int label_len, char* symbol,
                        int symbol_len) {
   return guard(h, [&]() -> int {
-    auto& p = h->eng->prof;
-    if (i < 0 || (size_t)i >= p.launches || (size_t)i >= p.lms.size())
-      throw dac::Error(DAC_E_ARG, "dac_profile_launch: index out of range (call dac_profile_read first)");
-    if (ms) *ms = p.lms[i];
-    if (flops) *flops = p.lflops[i];
-    if (bytes) *bytes = p.lbytes[i];
-    if (kernel_class) *kernel_class = p.lcls[i];
-    if (start_ms) *start_ms = (size_t)i < p.lt0.size() ? p.lt0[i] : -1.0;
-    if (in_branch) *in_branch = (size_t)i < p.lbranch.size() ? p.lbranch[i] : 0;
-    if (label && label_len > 0) snprintf(label, label_len, "%s", i < (int)p.labels.size() ? p.labels[i].c_str() : "");
-    if (symbol && symbol_len > 0) snprintf(symbol, symbol_len, "%s", i < (int)p.lsym.size() ? p.lsym[i].c_str() : "");
+    const dac::Launch& l = h->eng->prof.at(i);
+    if (ms) *ms = l.ms;
+    if (flops) *flops = l.flops;
+    if (bytes) *bytes = l.bytes;
+    if (kernel_class) *kernel_class = l.cls;
+    if (start_ms) *start_ms = l.t0_ms;
+    if (in_branch) *in_branch = l.in_branch ? 1 : 0;
+    if (label && label_len > 0) snprintf(label, label_len, "%s", l.label.c_str());
+    if (symbol && symbol_len > 0) snprintf(symbol, symbol_len, "%s", l.symbol.c_str());
     return DAC_OK;
   });
 }

@@ -308,31 +308,18 @@ struct Packer {
 };
 
 // ============================================================================= launches
-Profiler::~Profiler() {
-  for (auto e : ev) (void)hipEventDestroy(e);
-  if (sbuf) (void)hipFree(sbuf);
-}
-
-// Start of one timed launch: an event (eager replay) or the launch's stamp pair (graph mode).
-static unsigned long long* prof_begin(Profiler* p, hipStream_t st) {
-  if (p->stamps) {
-    if (p->used >= p->scap) throw Error(DAC_E_STATE, "profiler stamp slots not pre-allocated");
-    return p->sbuf + 2 * STAMP_SLOTS * p->used;
+// One launch of conv class `cls`, timed when the Run's profiler wants that class: launch(stamp)
+// enqueues it (stamp: the launch's stamp block in a stamped pass, else null). A dry run launches
+// nothing and counts the launches a live one will time; the label is only built for those.
+template <class Label, class Launcher>
+static void timed(Run& r, int cls, double flops, double bytes, Label&& make_label, Launcher&& launch) {
+  Profiler* p = r.prof && r.prof->wants(cls) ? r.prof : nullptr;
+  if (r.dry) {
+    if (p) p->counted++;
+    return;
   }
-  if (p->ev.size() < 2 * (p->used + 1)) throw Error(DAC_E_STATE, "profiler events not pre-created");
-  HIP_OK(hipEventRecord(p->ev[2 * p->used], st));
-  return nullptr;
-}
-static void prof_end(Profiler* p, const Run& r, int cls, double fl, double by) {
-  if (!p->stamps) HIP_OK(hipEventRecord(p->ev[2 * p->used + 1], r.st));
-  p->lbranch.push_back(r.in_branch ? 1 : 0);
-  p->used++;
-  p->launches++;
-  p->flops += fl;
-  p->bytes += by;
-  p->lcls.push_back(cls);
-  p->lflops.push_back(fl);
-  p->lbytes.push_back(by);
+  launch(p ? p->begin(r.st) : nullptr);
+  if (p) p->end(r.st, Launch{cls, flops, bytes, 0.0, -1.0, r.in_branch, make_label(), std::string()});
 }
 
 // The kernel arguments of a conv_call (the fused res_conv's fields included when requested).
@@ -391,7 +378,6 @@ void conv_call(Run& r, const ConvW& cw, const void* x1, int ld1, int C1, const v
       }
     }
   }
-  Profiler* p = r.prof;
   const bool use8 = sizeof(T) == 2 && cw.w8 && conv8_ok(a, cw.kh, cw.kw, stride, pad);
   // Per-image split-K at the small levels (g_splitk, UNetNet::forward): 3x3 convs over ks Cin
   // ranges; the count depends on one image's shape and the handle's policy, never on B.
@@ -433,42 +419,38 @@ void conv_call(Run& r, const ConvW& cw, const void* x1, int ld1, int C1, const v
   // Class 340: the fp8 ResBlock block2 (conv3q); an fp8-output block1 keeps its kernel's class.
   // Class 326: the row-phase upsample conv on v4 tiles (kept out of class 312's roofline).
   const int cls = cw.kh * 100 + (a.xs8 ? 40 : use8 ? 30 : a.uph ? 26 : conv_variant(a, cw.kh, (int)sizeof(T)));
-  const bool timed = p && (p->kernel_id == Profiler::ALL || p->kernel_id == cls);
-  if (r.dry) {
-    if (timed) p->used++;
-    return;
-  }
-  if (!cw.w) throw Error(DAC_E_STATE, "conv weight not loaded");
-  if (a.lnf_cs && !conv_lnf_ok(a, (int)sizeof(T))) throw Error(DAC_E_STATE, "conv: LN fold requested on a shape without a folding kernel");
-  if (a.gna_stats && !conv_gna_ok(a, (int)sizeof(T))) throw Error(DAC_E_STATE, "conv: GroupNorm A path requested on a shape without such a kernel");
-  if (a.ys8 && !conv_q8out_ok(a)) throw Error(DAC_E_STATE, "conv: fp8 output requested on a shape without such a kernel");
-  if (a.xs8 && !(sizeof(T) == 2 && cw.q8w && conv3q_ok(a))) throw Error(DAC_E_STATE, "conv: fp8 input on a layer without fp8 weights / kernel");
-  if (a.Cin % (16 / (int)sizeof(T)) || (a.x2 == nullptr && a.C1 < a.Cin))
-    throw Error(DAC_E_ARG, "conv: bad channel layout");
-  if (timed) a.stamp = prof_begin(p, r.st);
-  if (a.xs8) {
-    if constexpr (sizeof(T) == 2) conv3q<T>(a, cw.q8w, cw.q8s, r.st);
-  } else if (use8) {
-    if constexpr (sizeof(T) == 2) conv8<T>(a, cw.kh, cw.kw, stride, pad, cw.w8, cw.ws8, cw.kp8, r.st);
-  } else {
-    conv<T>(a, cw.kh, cw.kw, stride, pad, r.st);
-    if (dup1x1() && cw.kh == 1 && a.Ho * a.Wo <= 1024 && a.Ho * a.Wo >= 256 && a.ksplit <= 1) conv<T>(a, cw.kh, cw.kw, stride, pad, r.st);
-  }
-  emu_round<T>(r, y, ldy, (size_t)M, cw.cout);
-  if (fused) emu_round<T>(r, e.y2, e.ldy2, (size_t)M, cw.cout);
-  if (timed) {
+  // Algorithmic HBM bytes: every operand touched once (input, weights, output, residuals).
+  // (e4m3 tensors: 1 byte per value + 2 exponent bytes per pixel; e4m3 weights 1 byte.)
+  const double es = sizeof(T), ei = a.xs8 ? 1 + 2.0 / 64 : es, eo = a.ys8 ? 1 + 2.0 / 64 : es;
+  const double bytes = ei * B * Hs * Ws * cw.cin_real + (a.xs8 ? 1 : es) * cw.cout * cw.kh * cw.kw * cw.cin +
+                       M * cw.cout * (eo + es * ((e.res1 ? 1 : 0) + (e.res2 ? 1 : 0) + (fused ? 1 : 0)));
+  auto label = [&] {
     char lab[160];
     snprintf(lab, sizeof lab, "c%d %3dx%-3d%s B%d s%d %4d->%-4d%s%s%s%s%s", cls, Hs, Ws, up ? "^" : " ", B,
              stride, cw.cin_real, cw.cout, e.res1 ? " +r" : "", e.res2 ? " +r2" : "",
              e.ss ? " ss" : "", e.w_bstride ? " perimg" : "", fused ? " +1x1" : "");
-    p->labels.push_back(lab);
-    // Algorithmic HBM bytes: every operand touched once (input, weights, output, residuals).
-    // (e4m3 tensors: 1 byte per value + 2 exponent bytes per pixel; e4m3 weights 1 byte.)
-    const double es = sizeof(T), ei = a.xs8 ? 1 + 2.0 / 64 : es, eo = a.ys8 ? 1 + 2.0 / 64 : es;
-    prof_end(p, r, cls, fl,
-             ei * B * Hs * Ws * cw.cin_real + (a.xs8 ? 1 : es) * cw.cout * cw.kh * cw.kw * cw.cin +
-                 M * cw.cout * (eo + es * ((e.res1 ? 1 : 0) + (e.res2 ? 1 : 0) + (fused ? 1 : 0))));
-  }
+    return std::string(lab);
+  };
+  timed(r, cls, fl, bytes, label, [&](unsigned long long* stamp) {
+    if (!cw.w) throw Error(DAC_E_STATE, "conv weight not loaded");
+    if (a.lnf_cs && !conv_lnf_ok(a, (int)sizeof(T))) throw Error(DAC_E_STATE, "conv: LN fold requested on a shape without a folding kernel");
+    if (a.gna_stats && !conv_gna_ok(a, (int)sizeof(T))) throw Error(DAC_E_STATE, "conv: GroupNorm A path requested on a shape without such a kernel");
+    if (a.ys8 && !conv_q8out_ok(a)) throw Error(DAC_E_STATE, "conv: fp8 output requested on a shape without such a kernel");
+    if (a.xs8 && !(sizeof(T) == 2 && cw.q8w && conv3q_ok(a))) throw Error(DAC_E_STATE, "conv: fp8 input on a layer without fp8 weights / kernel");
+    if (a.Cin % (16 / (int)sizeof(T)) || (a.x2 == nullptr && a.C1 < a.Cin))
+      throw Error(DAC_E_ARG, "conv: bad channel layout");
+    a.stamp = stamp;
+    if (a.xs8) {
+      if constexpr (sizeof(T) == 2) conv3q<T>(a, cw.q8w, cw.q8s, r.st);
+    } else if (use8) {
+      if constexpr (sizeof(T) == 2) conv8<T>(a, cw.kh, cw.kw, stride, pad, cw.w8, cw.ws8, cw.kp8, r.st);
+    } else {
+      conv<T>(a, cw.kh, cw.kw, stride, pad, r.st);
+      if (dup1x1() && cw.kh == 1 && a.Ho * a.Wo <= 1024 && a.Ho * a.Wo >= 256 && a.ksplit <= 1) conv<T>(a, cw.kh, cw.kw, stride, pad, r.st);
+    }
+    emu_round<T>(r, y, ldy, (size_t)M, cw.cout);
+    if (fused) emu_round<T>(r, e.y2, e.ldy2, (size_t)M, cw.cout);
+  });
 }
 
 template <typename T>
@@ -885,22 +867,17 @@ struct UNetNet {
         ra.y = o;
         const double fl = 2.0 * M * 64 * 9 * (rb.c1.cin_real + 64) + (rb.has_res ? 2.0 * M * 64 * rb.c1.cin_real : 0.0);
         r.flops += fl;
-        Profiler* p = r.prof;
-        const bool timed = p && (p->kernel_id == Profiler::ALL || p->kernel_id == 350);
-        if (r.dry) {
-          if (timed) p->used++;
-          return o;
-        }
-        if (!rb.c1.w || !rb.c2.w || (rb.has_res && !rb.res.w)) throw Error(DAC_E_STATE, "conv weight not loaded");
-        if (timed) ra.stamp = prof_begin(p, r.st);
-        rbfuse<T>(ra, r.st);
-        if (timed) {
+        auto label = [&] {
           char lab[160];
           snprintf(lab, sizeof lab, "c350 %3dx%-3d  B%d ResBlock %4d->%-4d fused", H, W, B, rb.c1.cin_real, rb.dout);
-          p->labels.push_back(lab);
-          // Algorithmic HBM bytes: x in, y out.
-          prof_end(p, r, 350, fl, sizeof(T) * (double)M * (rb.c1.cin_real + rb.dout));
-        }
+          return std::string(lab);
+        };
+        // Algorithmic HBM bytes: x in, y out.
+        timed(r, 350, fl, sizeof(T) * (double)M * (rb.c1.cin_real + rb.dout), label, [&](unsigned long long* stamp) {
+          if (!rb.c1.w || !rb.c2.w || (rb.has_res && !rb.res.w)) throw Error(DAC_E_STATE, "conv weight not loaded");
+          ra.stamp = stamp;
+          rbfuse<T>(ra, r.st);
+        });
         return o;
       }
     }
@@ -1845,29 +1822,10 @@ class EngineT : public Engine {
     ensure_arena(plan(B, nT, c.has_ic, {{B, H, W}}));
     Bufs& b = get_bufs(B, H, W, nT);
     stage(b, c);
-    if (no_graph() && prof.kernel_id < 0) {
+    if (prof.on()) {
+      profile_pass(b, c);
+    } else if (no_graph()) {
       Run r = live(priv);
-      record_loop(r, b, c);
-    } else if (prof.kernel_id >= 0 && prof.stamps) {
-      profile_graph(b, c);
-    } else if (prof.kernel_id >= 0) {
-      // Profiling replay: HIP cannot report elapsed time between events recorded by graph
-      // nodes (hipEventElapsedTime -> invalid handle), so the same launch sequence runs
-      // eagerly on the same stream with an event pair around every launch of the class.
-      Arena da;
-      Run d = dry(da, false, &prof, zero_page);
-      prof.begin_pass();
-      record_loop(d, b, c);
-      while (prof.ev.size() < 2 * prof.used) {
-        hipEvent_t ev;
-        HIP_OK(hipEventCreate(&ev));
-        prof.ev.push_back(ev);
-      }
-      Run r = live(priv);
-      r.prof = &prof;
-      // per-launch event pairs time one stream: no side streams (nor in the dry pass above)
-      for (int k = 0; k < Run::kSide; ++k) r.side[k] = nullptr;
-      prof.begin_pass();
       record_loop(r, b, c);
     } else {
       const GKey key{c.mkey, B, H, W, nT};
@@ -1971,7 +1929,7 @@ class EngineT : public Engine {
                          int H, int W, const TileGrid& g, int tpf, int nT, const float* noise,
                          uint64_t seed, hipStream_t st) override {
     const LoopCall c = loop_call(mode, x, mu, tc, icx, B, H, W, nT, noise, seed, st, tpf);
-    if (prof.kernel_id >= 0)
+    if (prof.on())
       throw Error(DAC_E_STATE, "the tiled loop has no profiling mode (disable profiling first)");
     HIP_OK(hipSetDevice(dev));
     const int NT = B * (int)g.ys.size() * (int)g.xs.size();
@@ -2002,104 +1960,44 @@ class EngineT : public Engine {
     finish(L, c);
   }
 
-  // Graph-mode profiling (Profiler::stamps): the loop is recorded and captured exactly as the
-  // timed graph (same arena, side-stream branches, kernels and grids), with a [begin, end]
-  // wall-clock stamp pair in every launch of the profiled class(es); one replay, bracketed by
-  // HIP events on the loop's stream, gives every launch's in-graph duration. The kernel symbol
-  // of each launch is read back from the captured graph's kernel nodes (the stamp pointer in
-  // their argument block names the launch).
-  void profile_graph(Bufs& b, const LoopCall& c) {
+  // One profiled restore (profiler.h): a dry count of the launches of the profiled class(es),
+  // events or stamp slots for them, then the live recording.
+  // Eager pass: HIP cannot report elapsed time between events recorded by graph nodes
+  // (hipEventElapsedTime -> invalid handle), so the launch sequence runs eagerly on the loop's
+  // stream with an event pair around every timed launch; event pairs time one stream, so there
+  // are no side streams (nor in the dry count).
+  // Stamped pass: the loop is recorded and captured exactly as the timed graph (same arena,
+  // side-stream branches, kernels and grids), every timed launch writing its own wall-clock
+  // stamps; one replay, bracketed by HIP events on the loop's stream, gives every launch's
+  // in-graph duration, and the captured graph's kernel nodes name each launch's kernel symbol.
+  void profile_pass(Bufs& b, const LoopCall& c) {
+    const bool graph = prof.stamps;
     Arena da;
-    Run d = dry(da, true, &prof, zero_page);       // the same branch structure as the live capture
-    prof.begin_pass();
+    Run d = dry(da, graph, &prof, zero_page);
+    prof.begin_pass(Pass::counting);
     record_loop(d, b, c);
-    const size_t n = prof.used;
-    if (n > prof.scap) {
-      if (prof.sbuf) HIP_OK(hipFree(prof.sbuf));
-      prof.sbuf = nullptr;
-      prof.scap = 0;
-      HIP_OK(hipMalloc(&prof.sbuf, 2 * STAMP_SLOTS * n * sizeof(unsigned long long)));
-      prof.scap = n;
-    }
-    stamp_init(prof.sbuf, (size_t)STAMP_SLOTS * n, priv);
+    prof.prepare(priv);
     Run r = live(priv);
     r.prof = &prof;
-    prof.begin_pass();
+    if (graph) return profile_graph(r, b, c);
+    for (int k = 0; k < Run::kSide; ++k) r.side[k] = nullptr;
+    record_loop(r, b, c);
+    prof.check_complete();
+  }
+  void profile_graph(Run& r, Bufs& b, const LoopCall& c) {
     hipGraph_t g = capture([&] { record_loop(r, b, c); });
-    if (prof.used != n) {
-      (void)hipGraphDestroy(g);
-      throw Error(DAC_E_STATE, "profile_graph: dry and live recordings differ");
-    }
-    prof.lsym.assign(n, std::string());
-    size_t nn = 0;
-    if (hipGraphGetNodes(g, nullptr, &nn) == hipSuccess && nn) {
-      std::vector<hipGraphNode_t> nodes(nn);
-      if (hipGraphGetNodes(g, nodes.data(), &nn) == hipSuccess) {
-        for (size_t i = 0; i < nn; ++i) {
-          hipGraphNodeType ty;
-          if (hipGraphNodeGetType(nodes[i], &ty) != hipSuccess || ty != hipGraphNodeTypeKernel) continue;
-          hipKernelNodeParams kp{};
-          if (hipGraphKernelNodeGetParams(nodes[i], &kp) != hipSuccess || !kp.func || !kp.kernelParams ||
-              !kp.kernelParams[0])
-            continue;
-          const char* nm = hipKernelNameRefByPtr(kp.func, priv);
-          if (!nm) continue;
-          const std::string name(nm);
-          unsigned long long* sp = nullptr;
-          if (name.find("rbfuse_kernel") != std::string::npos)
-            sp = static_cast<const RbArgs*>(kp.kernelParams[0])->stamp;
-          else if (name.find("conv") != std::string::npos && name.find("_kernel") != std::string::npos)
-            sp = static_cast<const ConvArgs*>(kp.kernelParams[0])->stamp;
-          if (!sp || sp < prof.sbuf || sp >= prof.sbuf + 2 * STAMP_SLOTS * n) continue;
-          std::string& dst = prof.lsym[(size_t)(sp - prof.sbuf) / (2 * STAMP_SLOTS)];
-          dst = dst.empty() ? name : dst + "+" + name;
-        }
-      }
-    }
     hipGraphExec_t ex = nullptr;
-    const hipError_t ie = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    HIP_OK(ie);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
     try {
-      HIP_OK(hipEventCreate(&e0));
-      HIP_OK(hipEventCreate(&e1));
-      HIP_OK(hipEventRecord(e0, priv));
-      HIP_OK(hipGraphLaunch(ex, priv));
-      HIP_OK(hipEventRecord(e1, priv));
-      HIP_OK(hipEventSynchronize(e1));
-      float ms = 0;
-      HIP_OK(hipEventElapsedTime(&ms, e0, e1));
-      prof.graph_ms = ms;
-      std::vector<unsigned long long> hs(2 * STAMP_SLOTS * n);
-      HIP_OK(hipMemcpy(hs.data(), prof.sbuf, hs.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-      int khz = 0;
-      HIP_OK(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev));
-      if (khz <= 0) throw Error(DAC_E_HIP, "profile_graph: no wall-clock rate");
-      prof.lms.assign(n, 0.0);
-      prof.lt0.assign(n, 0.0);
-      unsigned long long origin = ~0ull;
-      for (size_t i = 0; i < n; ++i) {
-        unsigned long long b0 = ~0ull, b1 = 0;
-        for (int k = 0; k < STAMP_SLOTS; ++k) {                // slots no block used stay [max, 0]
-          b0 = std::min(b0, hs[2 * (STAMP_SLOTS * i + k)]);
-          b1 = std::max(b1, hs[2 * (STAMP_SLOTS * i + k) + 1]);
-        }
-        if (b0 == ~0ull || b1 < b0)
-          throw Error(DAC_E_STATE, "profile_graph: launch " + std::to_string(i) + " left no stamps");
-        prof.lms[i] = (double)(b1 - b0) / (double)khz;        // ticks / kHz = ms
-        prof.lt0[i] = (double)b0;
-        origin = std::min(origin, b0);
-      }
-      for (size_t i = 0; i < n; ++i) prof.lt0[i] = (prof.lt0[i] - (double)origin) / (double)khz;
+      prof.check_complete();
+      prof.name_symbols(g, priv);
+      HIP_OK(hipGraphInstantiate(&ex, g, nullptr, nullptr, 0));
+      prof.finish_stamps(ex, priv, dev);
     } catch (...) {
-      if (e0) (void)hipEventDestroy(e0);
-      if (e1) (void)hipEventDestroy(e1);
-      (void)hipGraphExecDestroy(ex);
+      (void)hipGraphDestroy(g);
+      if (ex) (void)hipGraphExecDestroy(ex);
       throw;
     }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    (void)hipGraphDestroy(g);
     HIP_OK(hipGraphExecDestroy(ex));
   }
 

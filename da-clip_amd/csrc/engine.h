@@ -1,34 +1,24 @@
 // engine.h — host-side runtime of libdaclip_hip: weight store (packing itself is pack.h),
 // workspace arena, and the network executors (ConditionalUNet, DaCLIP vision towers, IR-SDE loop).
+// The conv profiler the executors report to is profiler.h; dac::Error is error.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstring>
 #include <map>
 #include <memory>
-#include <stdexcept>
 #include <string>
 #include <unordered_map>
 #include <vector>
 
 #include "../../include/daclip_hip.h"
 #include "common.h"
+#include "error.h"
 #include "kernels.h"
 #include "pack.h"
+#include "profiler.h"
 
 namespace dac {
-
-struct Error : std::runtime_error {
-  int code;
-  Error(int c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
-
-#define HIP_OK(expr)                                                                      \
-  do {                                                                                    \
-    hipError_t e_ = (expr);                                                               \
-    if (e_ != hipSuccess)                                                                 \
-      throw ::dac::Error(DAC_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
-  } while (0)
 
 // ----------------------------------------------------------------------------- weights
 struct HostW {
@@ -96,38 +86,6 @@ struct Arena {
     if (off > cap) throw Error(DAC_E_NOMEM, "workspace arena overflow");
     return base + o;
   }
-};
-
-struct Profiler {
-  int kernel_id = -1;            // conv class to time (kh*100 + conv_variant), -1 = off
-  std::vector<hipEvent_t> ev;    // start/stop pairs
-  size_t used = 0;               // pairs recorded in the current pass
-  double flops = 0, bytes = 0;   // algorithmic work of the recorded launches
-  size_t launches = 0;
-  // kernel_id == ALL: every conv launch is timed and labelled by shape (per-shape report).
-  static constexpr int ALL = 999;
-  std::vector<std::string> labels;
-  std::vector<double> lflops;
-  // Per timed launch: conv class, algorithmic bytes, and (graph mode) measured duration and
-  // kernel symbol.
-  std::vector<int> lcls;
-  std::vector<double> lbytes, lms;
-  std::vector<double> lt0;       // graph mode: launch start (ms after the replay's first launch)
-  std::vector<char> lbranch;     // launched inside a concurrent branch of the UNet's split section
-  std::vector<std::string> lsym;
-  // Graph mode (dac_profile_mode 1): the next dac_sde_reverse records its loop into a captured
-  // graph exactly as the timed loop does (side-stream branches included), every timed launch
-  // carrying a [begin, end] wall-clock stamp pair (ConvArgs::stamp) in sbuf; one replay of that
-  // graph gives every launch's in-graph duration. graph_ms = the replay's HIP-event time.
-  bool stamps = false;
-  unsigned long long* sbuf = nullptr;
-  size_t scap = 0;
-  double graph_ms = 0;
-  void begin_pass() {
-    used = 0; flops = 0; bytes = 0; launches = 0; labels.clear(); lflops.clear();
-    lcls.clear(); lbytes.clear(); lms.clear(); lsym.clear(); lt0.clear(); lbranch.clear(); graph_ms = 0;
-  }
-  ~Profiler();
 };
 
 struct Run {
